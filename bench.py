@@ -34,13 +34,30 @@ compares its y slice with the oracle's opt_crs restatement of its own shard
 a bounded timeout (BENCH_PG_TIMEOUT_S, default 900 s), so a hung collective
 ends the job with an error.
 
+A plain run does only what the headline figure needs: it generates the
+matrix, builds the headline plan (the first of `--formats`), warms it up,
+times ONE trial of exactly K steps (`--trials T` asks for more), writes the
+outputs if `--dump-outputs` is given and prints the result line.  Everything
+else described here -- the other formats beside the headline, configs 3 and
+4, `max_rel_err_vs_cpu` against the oracle, `cpu_baseline`, `host_buffers`,
+the Mul / Sum phases, the measured STREAM / gather ceilings, and at N > 1
+`per_rank`, `collective_ms` and `iterative` -- takes runs of its own and is
+done with `--full` only (10 trials by default there); a plain line carries
+null in those fields.
+
+`--dump-outputs DIR` writes, after the timed steps, the y the headline plan
+computed in its last timed step as DIR/y.npy (float64; DIR/y_rank<k>.npy per
+rank at N > 1).  A y of more than 48 MB over all ranks is cut to a fixed
+sample of its entries (ascending indices drawn with seed 2024 from the rank's
+rows), so two builds given the same arguments write comparable files.
+
 `--gpus N` with no torchrun environment starts `torch.distributed.run` with N
 ranks (one per GPU) as a child process before anything in this process loads
 HIP (the GPUs are counted from the KFD topology in sysfs), and exits with the
 child's return code.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--trials T]
-                  [--config c2|c3|c4] [--formats auto,csr,ell,ss,css] [--only-config] [--no-cpu]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--trials T] [--dump-outputs DIR]
+                  [--full] [--config c2|c3|c4] [--formats auto,csr,ell,ss,css] [--only-config] [--no-cpu]
 
 Prints ONE JSON line on rank 0.
 """
@@ -159,9 +176,17 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--trials", type=int, default=10,
+    ap.add_argument("--trials", type=int, default=None,
                     help="timed trials of K steps of each config's headline plan; value = the fastest "
-                         "(src/main.cpp:58-102: min of 10); the other formats get 3")
+                         "(default: 1, so that --steps is the number of timed steps; with --full 10, "
+                         "src/main.cpp:58-102: min of 10, and the other formats get 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the other formats, configs 3 / 4, the check "
+                         "against the oracle, cpu_baseline, host_buffers, phases, measured ceilings, and at "
+                         "N > 1 per_rank / collective_ms / iterative")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline plan's y of its last timed step to "
+                         "DIR/y.npy (float64; a fixed seeded sample when larger than 48 MB)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--rows", type=int, default=0, help="rows per GPU (default: the config's)")
     ap.add_argument("--formats", default=None,
@@ -181,7 +206,10 @@ def parse():
     ap.add_argument("--sim-world", type=int, default=0,
                     help="development: run rank 0's share of a K-GPU job on one GPU "
                          "(n = K * rows); the JSON marks it as emulated")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.trials is None:
+        args.trials = 10 if args.full else 1
+    return args
 
 
 def visible_gpu_count(topology: str = None) -> int:
@@ -402,6 +430,8 @@ def time_formats(ctx, args, M, fmts, trials_head: int, y_check=None, setup_mark=
             wall = time.perf_counter() - tw
             wall_max = ctx.sdist.max_over_ranks([wall], ctx.dev)[0]
             trials.append((wall_max, ev_ms, wall))
+        if fi == 0:
+            y_head = y.clone()  # the y of the headline's last timed step (--dump-outputs)
         wall_max, ev_ms, wall_own = min(trials)
         launch_s = ev_ms / 1e3 / args.steps
         algo = model_bytes(info["format"], M["rows"], M["n"], M["nnz_local"], info.get("n_diags", 0))
@@ -424,7 +454,7 @@ def time_formats(ctx, args, M, fmts, trials_head: int, y_check=None, setup_mark=
         }
         for k in RELEVANT.get(info["format"], ()):
             r[k] = info[k]
-        if info["n_kernels"] > 1:
+        if args.full and info["n_kernels"] > 1:
             r["phases_ms"] = plan.profile(M["x"], y, 10)  # e.g. BIN Mul / Sum (opt_ss MulPerf / SumPerf)
         tb, kind = lookup_traffic(M["config"], M["rows"], M["n"], info["kernel"])
         if tb is not None:
@@ -439,7 +469,6 @@ def time_formats(ctx, args, M, fmts, trials_head: int, y_check=None, setup_mark=
         results[fmt if fmt not in results else f"{fmt}_{fi}"] = r
         if fi == 0:
             headline = (plan, info, r)
-            y_head = y.clone()
         else:
             plan.destroy()
         torch.cuda.synchronize()
@@ -557,6 +586,36 @@ def extra_config(ctx, args, config: str, fmts, stream_gbs: float) -> dict:
     return out
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: all ranks' files together (float64 entries)
+DUMP_SEED = 2024
+
+
+def dump_sample_index(rows: int, world: int):
+    """Ascending indices of the y entries --dump-outputs keeps of a rank's
+    `rows` (None = all of them): every rank gets an equal share of the budget,
+    the sample depends on (rows, world) only."""
+    keep = DUMP_BUDGET_BYTES // 8 // max(1, world)
+    if rows <= keep:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=keep, replace=False))
+
+
+def dump_outputs(ctx, path: str, y) -> dict:
+    """Write this rank's y (what a caller of plan.execute receives), or its
+    fixed sample, as float64 .npy under `path`."""
+    os.makedirs(path, exist_ok=True)
+    idx = dump_sample_index(int(y.numel()), ctx.world)
+    ctx.torch.cuda.synchronize()
+    if idx is None:
+        arr = y.cpu().numpy()
+    else:
+        arr = y[ctx.torch.from_numpy(idx).to(y.device)].cpu().numpy()
+    name = "y.npy" if ctx.world == 1 else f"y_rank{ctx.rank}.npy"
+    np.save(os.path.join(path, name), np.ascontiguousarray(arr, dtype=np.float64))
+    return {"dir": path, "file": name, "entries": int(arr.size), "of": int(y.numel()),
+            "sampled": idx is not None, "sample_seed": DUMP_SEED if idx is not None else None}
+
+
 def main():
     args = parse()
     rc = self_launch(args)
@@ -590,20 +649,26 @@ def main():
 
     fmts_arg = args.formats or ("auto,csr,ell,ss,css" if world == 1 else "auto,csr")
     fmts = [f for f in fmts_arg.split(",") if f]
-    # every rank's oracle y of its own shard: each format's y is checked
-    # against it after that format's timed trials, at every N
-    y_check, t_check_ms = shard_check(M)
-    progress(f"{args.config}: oracle y of this rank's shard in {t_check_ms:.0f} ms")
+    full = args.full
+    y_check = None
+    if full:
+        # every rank's oracle y of its own shard: each format's y is checked
+        # against it after that format's timed trials, at every N
+        y_check, t_check_ms = shard_check(M)
+        progress(f"{args.config}: oracle y of this rank's shard in {t_check_ms:.0f} ms")
+    else:
+        fmts = fmts[:1]  # the headline plan alone
     results, headline, y_head = time_formats(ctx, args, M, fmts, args.trials, y_check=y_check, setup_mark=True)
     if headline is None:
         if rank == 0:
             print(json.dumps({"error": "no plan could be built", "details": results}))
         return 1
     plan, info, r = headline
+    dumped = dump_outputs(ctx, args.dump_outputs, y_head) if args.dump_outputs else None
 
     # per-rank view of the headline step (the value is the max over ranks)
     per_rank = None
-    if distributed:
+    if full and distributed:
         ph = r.get("phases_ms", {})
         su = M.get("setup", {})
         rows_all = sdist.gather_floats([float(rank), float(M["row0"]), float(M["row1"]), float(nnz_local),
@@ -626,7 +691,7 @@ def main():
     # (slices padded to the longest rank's rows)
     rows_max = int(np.max(np.diff(M["cuts"]))) if distributed else rows
     coll_ms = None
-    if distributed:
+    if full and distributed:
         for _ in range(3):
             sdist.gather_y(y_head, rows_max)
         torch.cuda.synchronize()
@@ -644,7 +709,7 @@ def main():
     # never as it.  Runs on a copy of x; needs equal slices (uniform rows).
     iterative = None
     equal_slices = bool(np.all(np.diff(M["cuts"]) == rows)) and n_glob == rows * world
-    if distributed and equal_slices:
+    if full and distributed and equal_slices:
         x_it = x.clone()
         cur = torch.cuda.current_stream(dev)
         plan.set_stream(cur)
@@ -668,7 +733,7 @@ def main():
     # the drop-in's host-buffer mode (opt_cusparse's per-call H2D x / D2H y,
     # src/opt_cusparse.cpp:72,82): PCIe-inclusive, reported beside `value`
     host_mode = None
-    if rank == 0 and world == 1:
+    if full and rank == 0 and world == 1:
         xh = np.ascontiguousarray(x.cpu().numpy())
         yh = np.empty(rows, np.float64)
         reps = 5
@@ -710,8 +775,8 @@ def main():
     # (profiles/round2/cpu_ref_vs_port.json).
     cpu = None
     # the headline's y against the oracle, max over every rank's slice
-    max_rel = r["max_rel_err_vs_cpu"]
-    if rank == 0 and world == 1 and not args.no_cpu:
+    max_rel = r.get("max_rel_err_vs_cpu")
+    if full and rank == 0 and world == 1 and not args.no_cpu:
         import oracle
         nthreads = min(host_cores, int(os.environ.get("OMP_NUM_THREADS", host_cores)))
         x_host = x.cpu().numpy()
@@ -738,15 +803,17 @@ def main():
 
     # measured ceilings of this GPU (reported beside the spec peak)
     local = ctx.local
-    stream_gbs = sp.stream_probe(local, 2 << 30, 10)
-    stream_write_gbs = sp.stream_write_probe(local, 2 << 30, 10)
-    mixed_gbs = sp.mixed_probe(local, 1792 << 20, 3, 20)
-    # random 8-byte x gathers that hit L2 (CSS's slab), and from a table of
-    # x's own size (the row-parallel formats' gathers)
-    gather_gps = sp.gather_probe(local, 64 << 20, 1 << 20)
-    gather_x_gps = sp.gather_probe(local, 64 << 20, min(max(8 * n_glob, 1 << 20), 2 << 30))
+    stream_gbs = stream_write_gbs = mixed_gbs = gather_gps = gather_x_gps = None
+    if full:
+        stream_gbs = sp.stream_probe(local, 2 << 30, 10)
+        stream_write_gbs = sp.stream_write_probe(local, 2 << 30, 10)
+        mixed_gbs = sp.mixed_probe(local, 1792 << 20, 3, 20)
+        # random 8-byte x gathers that hit L2 (CSS's slab), and from a table of
+        # x's own size (the row-parallel formats' gathers)
+        gather_gps = sp.gather_probe(local, 64 << 20, 1 << 20)
+        gather_x_gps = sp.gather_probe(local, 64 << 20, min(max(8 * n_glob, 1 << 20), 2 << 30))
     for fr in results.values():
-        if "event_ms_per_launch" not in fr:
+        if not full or "event_ms_per_launch" not in fr:
             continue
         fr["frac_of_stream"] = fr["achieved_gbs"] / stream_gbs
         fr["roofline_frac"] = fr["achieved_gbs"] / HBM_PEAK_GBS
@@ -762,16 +829,18 @@ def main():
     # charges x per nnz -- for comparability with published CSR5 numbers only
     csr5_bytes = (rows + 1 + nnz_local) * 4 + (2 * nnz_local + rows) * 8
     roof = roofline_of(args.config, M, r)
-    roof.update({"stream_ceiling_gbs": stream_gbs, "frac_of_stream": r["achieved_gbs"] / stream_gbs,
-                 "stream_write_gbs": stream_write_gbs, "mixed_rw_gbs": mixed_gbs,
-                 "csr5_model_gbs": csr5_bytes / (r["event_ms_per_launch"] * 1e-3) / 1e9})
-    if "traffic_gbs" in roof:
-        roof["traffic_frac_of_stream"] = roof["traffic_gbs"] / stream_gbs
+    roof["csr5_model_gbs"] = csr5_bytes / (r["event_ms_per_launch"] * 1e-3) / 1e9
+    if full:
+        roof.update({"stream_ceiling_gbs": stream_gbs, "frac_of_stream": r["achieved_gbs"] / stream_gbs,
+                     "stream_write_gbs": stream_write_gbs, "mixed_rw_gbs": mixed_gbs})
+        if "traffic_gbs" in roof:
+            roof["traffic_frac_of_stream"] = roof["traffic_gbs"] / stream_gbs
     out = {
         "metric": "SpMV GFLOP/s (fp64) + achieved HBM GB/s",
         "value": r["gflops"],
         "unit": "GFLOP/s",
         "n_gpus": world,
+        "full": full,
         "steps": args.steps,
         "warmup": args.warmup,
         "trials": args.trials,
@@ -794,7 +863,7 @@ def main():
         # the headline's launch time over it is how close the kernels are
         "ceiling": (_bin_ceiling_line(streamed_bytes(info), stream_gbs, stream_write_gbs, mixed_gbs, nnz_local,
                                       r["event_ms_per_launch"])
-                    if info["format"] == "bin" else None),
+                    if full and info["format"] == "bin" else None),
         "formats": results,
         "per_rank": per_rank,
         "gen_s": round(M["gen_s"], 2),
@@ -803,10 +872,12 @@ def main():
         "iterative": iterative,
         "host_buffers": host_mode,
         "max_rel_err_vs_cpu": max_rel,
-        "check": "every format's y, on every rank, against the oracle's opt_crs restatement of that rank's "
-                 "shard (oracle/oracle.c, src/opt_crs.cpp:44-70), after its timed trials; max over ranks",
+        "check": ("every format's y, on every rank, against the oracle's opt_crs restatement of that rank's "
+                  "shard (oracle/oracle.c, src/opt_crs.cpp:44-70), after its timed trials; max over ranks"
+                  if full else "not run (--full checks every format's y against the oracle)"),
         "verify_max_rel": verify_rel,
-        "gather_ceilings_per_s": {"l2_table": gather_gps, "x_table": gather_x_gps},
+        "gather_ceilings_per_s": {"l2_table": gather_gps, "x_table": gather_x_gps} if full else None,
+        "dumped_outputs": dumped,
     }
     if ctx.shape_world != world:
         out["emulated_world"] = ctx.shape_world
@@ -816,7 +887,7 @@ def main():
     torch.cuda.empty_cache()
 
     # configs 3 and 4 beside the N = 1 headline (BASELINE.json configs[2-3])
-    if world == 1 and not args.only_config and not args.sim_world and not args.rows and args.config == "c2":
+    if full and world == 1 and not args.only_config and not args.sim_world and not args.rows and args.config == "c2":
         out["configs"] = {c: extra_config(ctx, args, c, f, stream_gbs) for c, f in EXTRA_CONFIGS}
 
     if rank == 0:

@@ -36,7 +36,7 @@ def test_two_rank_bench_flow(config, fmts, launch):
                 "--master-addr", "127.0.0.1", "--master-port", str(_free_port())]
     cmd = pre + [os.path.join(ROOT, "bench.py"),
                  "--gpus", "2", "--steps", "3", "--warmup", "1", "--trials", "2", "--rows", "150000",
-                 "--config", config, "--formats", fmts, "--verify", "--no-cpu"]
+                 "--config", config, "--formats", fmts, "--verify", "--no-cpu", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -68,7 +68,7 @@ def test_power_law_shards_are_nnz_balanced(ranks):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "3", "--warmup", "1",
-           "--trials", "1", "--rows", "500000", "--config", "c3", "--formats", "auto", "--no-cpu"]
+           "--trials", "1", "--rows", "500000", "--config", "c3", "--formats", "auto", "--no-cpu", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -83,6 +83,61 @@ def test_power_law_shards_are_nnz_balanced(ranks):
     errs = [p["max_rel_err_vs_cpu"] for p in d["per_rank"]]
     assert all(0 <= e <= 1e-12 for e in errs), errs
     assert d["max_rel_err_vs_cpu"] == max(errs)
+
+
+def test_plain_bench_times_the_headline_alone_and_dumps_its_y(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`:
+    one trial of K steps of the headline plan alone, nothing that takes runs
+    of its own (null in the line), and DIR/y.npy = the y of the last timed
+    step in float64 -- bit for bit the oracle's on the same seeded matrix
+    (BIN sums each row in column order), so the same file from every run."""
+    import numpy as np
+    import oracle
+    import singlespmv_amd as sp
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
+        env.pop(k, None)
+    m = 150_000
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--rows", str(m), "--formats", "bin,csr", "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["trials"] == 1 and d["full"] is False
+    assert d["unit"] == "GFLOP/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["ms_per_step"] > 0 and len(d["formats"]["bin"]["trials_ms_per_step"]) == 1
+    assert abs(d["value"] - 2.0 * d["config"]["nnz_total"] / (d["ms_per_step"] * 1e-3) / 1e9) <= 1e-9 * d["value"]
+    assert list(d["formats"]) == ["bin"] and "configs" not in d
+    for k in ("cpu_baseline", "host_buffers", "phases_ms", "ceiling", "max_rel_err_vs_cpu", "per_rank",
+              "collective_ms", "iterative", "gather_ceilings_per_s"):
+        assert d[k] is None, k
+    assert d["dumped_outputs"]["entries"] == m and d["dumped_outputs"]["sampled"] is False
+    assert sorted(os.listdir(tmp_path / "out")) == ["y.npy"]
+    y = np.load(tmp_path / "out" / "y.npy")
+    assert y.dtype == np.float64 and y.shape == (m,)
+    rp, col, val = sp.generate_csr(sp.gen_spec("uniform", m, m, per_row=16, seed=42))
+    assert np.array_equal(y, oracle.csr_spmv(rp, col, val, sp.generate_vector(m, seed=43)))
+
+
+def test_dump_outputs_writes_the_seeded_sample_of_a_large_y(tmp_path, monkeypatch):
+    """bench.dump_outputs on a y beyond the budget: the file holds exactly the
+    entries bench.dump_sample_index names, in that order."""
+    import types
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8 * 1000)
+    y = torch.arange(5000, dtype=torch.float64, device="cuda:0") * 0.5
+    rec = bench.dump_outputs(types.SimpleNamespace(torch=torch, world=1, rank=0), str(tmp_path / "d"), y)
+    idx = bench.dump_sample_index(5000, 1)
+    got = np.load(tmp_path / "d" / rec["file"])
+    assert rec["sampled"] and rec["entries"] == 1000 and rec["of"] == 5000
+    assert got.dtype == np.float64 and np.array_equal(got, idx * 0.5)
+    assert len(idx) == 1000 and np.all(np.diff(idx) > 0) and idx[-1] < 5000
 
 
 def test_c_abi_dist_plan_one_device():

@@ -170,6 +170,31 @@ def test_bench_self_launch(monkeypatch):
     assert bench.self_launch(bench.parse()) == 2  # mismatched launcher: refuse
 
 
+def test_bench_plain_run_defaults_and_dump_sample(monkeypatch):
+    """A plain `bench.py --steps K` times ONE trial of K steps (--full: 10,
+    an explicit --trials wins), and the --dump-outputs sample is a fixed
+    function of (rows, world): ascending, within the rows, 48 MB of float64
+    over all ranks, the whole y when it is smaller."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.trials, a.full, a.dump_outputs) == (7, 2, 1, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert (a.trials, a.full, a.dump_outputs) == (10, True, "d")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--trials", "3"])
+    assert bench.parse().trials == 3
+    assert bench.dump_sample_index(1000, 1) is None
+    assert bench.dump_sample_index(bench.DUMP_BUDGET_BYTES // 8, 1) is None
+    rows = 10_000_000
+    for world in (1, 8):
+        idx = bench.dump_sample_index(rows, world)
+        assert len(idx) * 8 * world <= 64 << 20 and len(idx) == bench.DUMP_BUDGET_BYTES // 8 // world
+        assert idx[0] >= 0 and idx[-1] < rows and np.all(np.diff(idx) > 0)
+        assert np.array_equal(idx, bench.dump_sample_index(rows, world))
+
+
 def test_bench_self_launch_parent_stays_off_hip(tmp_path):
     """The self-launching parent counts GPUs from the KFD topology and spawns
     the launcher without loading HIP: in a fresh interpreter, a fake launcher

@@ -19,6 +19,6 @@ for CTRS in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY
   i=$((i + 1))
   # shellcheck disable=SC2086
   timeout -s KILL 300 rocprofv3 --kernel-trace --pmc $CTRS --output-format csv -d $OUT/pass$i -o run -- \
-      python3 $R/bench.py --no-cpu "$@" > $OUT/pass$i.json 2> $OUT/pass$i.err || exit $?
+      python3 $R/bench.py --full --no-cpu "$@" > $OUT/pass$i.json 2> $OUT/pass$i.err || exit $?
 done
 python3 $R/tools/pmc_stalls_summary.py $OUT > $OUT/summary.json
