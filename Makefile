@@ -30,7 +30,7 @@ KERN_SRC  = $(CSRC)/k_csr.hip $(CSRC)/k_ell.hip $(CSRC)/k_ss.hip $(CSRC)/k_dia.h
 HOST_OBJ  = $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(HOST_SRC))
 KERN_OBJ  = $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(KERN_SRC))
 HDRS      = include/spmv_hip.h include/opt_hip.h include/spmv_util.h \
-            $(CSRC)/internal.hpp $(CSRC)/device.hpp
+            $(CSRC)/internal.hpp $(CSRC)/device.hpp $(CSRC)/build_util.hpp
 
 all: $(LIB) $(OPTLIB) bin/spmv bin/csr5_api bin/gather_probe oracle
 

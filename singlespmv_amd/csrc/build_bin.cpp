@@ -18,44 +18,9 @@
 #include <cstdlib>
 #include <vector>
 
-#include "internal.hpp"
+#include "build_util.hpp"
 
 namespace spmv {
-
-template <typename T>
-static int upload_vec(spmv_plan_s *p, T **dst, const std::vector<T> &src) {
-    void *q = nullptr;
-    SPMV_RETURN_IF(p->arena.alloc(&q, sizeof(T) * std::max<size_t>(src.size(), 1)));
-    if (!src.empty()) SPMV_HIP_TRY(hipMemcpy(q, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
-    *dst = (T *)q;
-    return SPMV_SUCCESS;
-}
-
-// Host-side layout shared by the two builders.
-struct BinLayout {
-    int64_t S = 0, NB = 0, E = 0, PAD = 16;
-    std::vector<int32_t> row0;          // [NB + 1]
-    std::vector<int32_t> cnt;           // [NB * S] entries per (bin, strip)
-    std::vector<int64_t> off1, off2;    // [NB * S] segment start, Mul / Sum order
-    std::vector<int64_t> run_off;       // [NBK * NB + 1]
-    std::vector<int64_t> srun_off;      // [NBK * NB + 1] slot runs, each padded to 64*sum_u
-    int64_t ES = 0, SB = 1;             // slot entries; strips per block
-    std::vector<int64_t> strip_start;   // [G * (S + 1)] Mul-order start of (group, strip)
-    std::vector<int64_t> mul_bins;      // [NB] bins in Mul visiting order within each strip (per group)
-    // long rows (internal.hpp BinDev, the run path); LL = 0: none
-    int64_t LL = 0, NP = 0, E1 = 0, TRASH = 0;
-    std::vector<int64_t> eff_rp;        // [m + 1] cumulative Sum entries per row (bin cut)
-    std::vector<int64_t> lb_off;        // [S + 1] long entries of strip t in lb_j / lb_row
-    std::vector<int64_t> lb_j;          // entry index, ordered [strip][row][CSR order]
-    std::vector<int32_t> lb_row;
-    std::vector<int32_t> lpc;           // [NB * S] run pieces of (bin, strip)
-    std::vector<int64_t> lpoff;         // [NB * S] product position of (bin, strip)'s first piece
-    std::vector<int64_t> lpad;          // [S] long entries of strip t, padded to 64
-    std::vector<int64_t> lstart;        // [S] Mul position of strip t's first long block
-    std::vector<int64_t> lcode_off;     // [S] lcode index of the same
-    int64_t rpad(int64_t v) const { return (v + PAD - 1) & ~(PAD - 1); }
-    bool is_long(const int64_t *rp, int64_t r) const { return LL > 0 && rp[r + 1] - rp[r] >= LL; }
-};
 
 // ---- parameters (strip width, workgroups, padding, Sum waves) -----------
 static int bin_params(spmv_plan_s *p, const spmv_options_t &o, int64_t m, int64_t n, int64_t nnz) {
@@ -609,15 +574,15 @@ static int bin_fill_host(spmv_plan_s *p, const HostCsr &A, const BinLayout &L) {
     BinHostArrays H;
     bin_fill_arrays(B, A, L, H);
     if (L.LL > 0) {
-        SPMV_RETURN_IF(upload_vec(p, &B.lcode, H.lcode));
-        SPMV_RETURN_IF(upload_vec(p, &B.lstart, L.lstart));
-        SPMV_RETURN_IF(upload_vec(p, &B.lshift, H.lshift));
+        SPMV_RETURN_IF(plan_upload(p, &B.lcode, H.lcode));
+        SPMV_RETURN_IF(plan_upload(p, &B.lstart, L.lstart));
+        SPMV_RETURN_IF(plan_upload(p, &B.lshift, H.lshift));
     }
-    SPMV_RETURN_IF(upload_vec(p, &B.val1, H.val1));
-    SPMV_RETURN_IF(upload_vec(p, &B.cs1, H.cs1));
-    if (B.mo) SPMV_RETURN_IF(upload_vec(p, &B.mtab, H.mtab));
-    else SPMV_RETURN_IF(upload_vec(p, &B.dst1, H.dst1));
-    SPMV_RETURN_IF(upload_vec(p, &B.slot2, H.slot2));
+    SPMV_RETURN_IF(plan_upload(p, &B.val1, H.val1));
+    SPMV_RETURN_IF(plan_upload(p, &B.cs1, H.cs1));
+    if (B.mo) SPMV_RETURN_IF(plan_upload(p, &B.mtab, H.mtab));
+    else SPMV_RETURN_IF(plan_upload(p, &B.dst1, H.dst1));
+    SPMV_RETURN_IF(plan_upload(p, &B.slot2, H.slot2));
     return SPMV_SUCCESS;
 }
 
@@ -631,10 +596,7 @@ static int alloc_prod_plain(spmv_plan_s *p, size_t prod_bytes) {
     // (hipDeviceMallocContiguous was tried for the product buffer: plans built
     // after another plan was freed returned WRONG sums -- the buffer behaved
     // as if aliased -- so it is not used; tools/dbg_bin.py reproduces it.)
-    void *q = nullptr;
-    SPMV_RETURN_IF(p->arena.alloc(&q, prod_bytes));
-    p->bin.prod = (double *)q;
-    return SPMV_SUCCESS;
+    return plan_alloc(p, &p->bin.prod, (int64_t)(prod_bytes / sizeof(double)));
 }
 
 // SPMV_PLACEMENT_SEARCH: keep the fastest of up to K candidates, each timed
@@ -809,13 +771,13 @@ static int bin_finish(spmv_plan_s *p, int64_t n, const BinLayout &L, const spmv_
     if (B.reuse)
         for (int g = 0; g < B.G; ++g) B.prod_cap = std::max(B.prod_cap, B.g_prod[(size_t)g + 1] - B.g_prod[(size_t)g]);
     const size_t prod_bytes = sizeof(double) * (size_t)(std::max<int64_t>(B.prod_cap, 1) + kBinProdSlack);
-    SPMV_RETURN_IF(upload_vec(p, &B.piece_off, piece_off));
-    SPMV_RETURN_IF(upload_vec(p, &B.piece_strip, pstrip));
-    SPMV_RETURN_IF(upload_vec(p, &B.piece_begin, pbeg));
-    SPMV_RETURN_IF(upload_vec(p, &B.piece_end, pend));
-    SPMV_RETURN_IF(upload_vec(p, &B.run_off, L.run_off));
-    SPMV_RETURN_IF(upload_vec(p, &B.srun_off, L.srun_off));
-    SPMV_RETURN_IF(upload_vec(p, &B.bin_row0, L.row0));
+    SPMV_RETURN_IF(plan_upload(p, &B.piece_off, piece_off));
+    SPMV_RETURN_IF(plan_upload(p, &B.piece_strip, pstrip));
+    SPMV_RETURN_IF(plan_upload(p, &B.piece_begin, pbeg));
+    SPMV_RETURN_IF(plan_upload(p, &B.piece_end, pend));
+    SPMV_RETURN_IF(plan_upload(p, &B.run_off, L.run_off));
+    SPMV_RETURN_IF(plan_upload(p, &B.srun_off, L.srun_off));
+    SPMV_RETURN_IF(plan_upload(p, &B.bin_row0, L.row0));
     // the run path is part of the launch the placement search times
     B.long_len = L.LL;
     SPMV_RETURN_IF(bin_place_prod(p, n, prod_bytes, o));
@@ -906,13 +868,13 @@ struct BinDevLong {
     std::vector<int64_t> order;         // the runs sorted [strip][row]
 };
 
-static int bin_long_prep_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col,
-                                const std::vector<int64_t> &rp, BinLayout &L, BinDevLong &D) {
+static int bin_long_prep_device(spmv_plan_s *p, const DevCsr &A, BinLayout &L, BinDevLong &D) {
     const int64_t m = p->m, S = L.S;
+    const int64_t *rp = A.h_rp;
     D = BinDevLong();
     for (int64_t r = 0; r < m; ++r)
-        if (L.is_long(rp.data(), r)) D.lrows.push_back((int32_t)r);
-    SPMV_RETURN_IF(bin_long_runs_device(p, d_rp, d_col, D.lrows, D.roff, D.rstrip, D.rbeg));
+        if (L.is_long(rp, r)) D.lrows.push_back((int32_t)r);
+    SPMV_RETURN_IF(bin_long_runs_device(p, A, D.lrows, D.roff, D.rstrip, D.rbeg));
     const int64_t nl = (int64_t)D.lrows.size(), R = D.roff[(size_t)nl];
     D.rlen.resize((size_t)R);
     // Sum entries per row: a long row needs one per strip it touches and one
@@ -1017,18 +979,16 @@ static void bin_long_runs_table(const BinLayout &L, const BinDevLong &D, BinLong
     });
 }
 
-static int build_bin_device_impl(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, const double *d_val,
-                                 const spmv_options_t &o) {
+static int build_bin_device_impl(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o) {
     BinDev &B = p->bin;
     SPMV_RETURN_IF(bin_params(p, o, p->m, p->n, p->nnz));
     if (p->m == 0 || p->nnz == 0) {
         B.G = 0;
         return SPMV_SUCCESS;
     }
-    std::vector<int64_t> rp((size_t)p->m + 1);
-    SPMV_HIP_TRY(hipMemcpy(rp.data(), d_rp, 8 * (size_t)(p->m + 1), hipMemcpyDeviceToHost));
+    const int64_t *rp = A.h_rp;
     const int64_t S = std::max<int64_t>(1, (p->n + B.strip - 1) / B.strip);
-    int64_t LL = bin_long_threshold(o, rp.data(), p->m, p->nnz, S);
+    int64_t LL = bin_long_threshold(o, rp, p->m, p->nnz, S);
     // bin_layout's loop: long rows take the run path when their product
     // positions fit lcode, else the layout is redone without it
     BinLayout L;
@@ -1040,14 +1000,14 @@ static int build_bin_device_impl(spmv_plan_s *p, const int64_t *d_rp, const int3
         L.LL = LL;
         B.long_rows = 0;
         if (LL > 0) {
-            SPMV_RETURN_IF(bin_long_prep_device(p, d_rp, d_col, rp, L, D));
+            SPMV_RETURN_IF(bin_long_prep_device(p, A, L, D));
             B.long_rows = (int64_t)D.lrows.size();
         }
         bin_mo_resolve(B, o, LL, p->nnz);
-        SPMV_RETURN_IF(bin_rows(p, rp.data(), p->m, p->n, L));
+        SPMV_RETURN_IF(bin_rows(p, rp, p->m, p->n, L));
         bstart.assign((size_t)L.NB + 1, 0);
         for (int64_t b = 0; b <= L.NB; ++b) bstart[(size_t)b] = rp[(size_t)L.row0[(size_t)b]];
-        const int st = bin_count_device(p, d_rp, d_col, L.row0, bstart, L.S, LL, L.cnt);
+        const int st = bin_count_device(p, A, L.row0, bstart, L.S, LL, L.cnt);
         if (st != SPMV_SUCCESS) return st;  // kBinNeedHostBuild: unsorted rows
         if (LL > 0) bin_long_count_device(L, D);
         bin_offsets(p, o, L);
@@ -1057,51 +1017,40 @@ static int build_bin_device_impl(spmv_plan_s *p, const int64_t *d_rp, const int3
         }
         break;
     }
-    std::vector<int64_t>().swap(rp);
-    SPMV_RETURN_IF(bin_fill_device(p, d_rp, d_col, d_val, L.row0, bstart, L.cnt, L.off1, L.off2, L.run_off,
-                                   L.srun_off, L.S, L.E, L.ES, LL, L.E1,
-                                   (int32_t)(L.TRASH >> B.pad_log)));
+    SPMV_RETURN_IF(bin_fill_device(p, A, L, bstart, (int32_t)(L.TRASH >> B.pad_log)));
     if (LL > 0) {
         BinLongRuns LR;
         bin_long_runs_table(L, D, LR);
         D = BinDevLong();
-        SPMV_RETURN_IF(bin_long_fill_device(p, d_col, d_val, LR, L.lb_off, L.lpad, L.lstart, L.lcode_off, L.run_off,
-                                            L.srun_off, (B.n_blocks - 1) * L.NB, L.TRASH));
+        SPMV_RETURN_IF(bin_long_fill_device(p, A, L, LR, (B.n_blocks - 1) * L.NB));
         std::vector<int64_t> lshift((size_t)S);
         for (int64_t t = 0; t < S; ++t) lshift[(size_t)t] = L.lcode_off[(size_t)t] - L.lstart[(size_t)t];
-        SPMV_RETURN_IF(upload_vec(p, &B.lstart, L.lstart));
-        SPMV_RETURN_IF(upload_vec(p, &B.lshift, lshift));
+        SPMV_RETURN_IF(plan_upload(p, &B.lstart, L.lstart));
+        SPMV_RETURN_IF(plan_upload(p, &B.lshift, lshift));
     }
     if (B.mo) {  // the chunk table needs only the layout
         std::vector<int32_t> tab;
         bin_mo_table(B, L, tab);
-        SPMV_RETURN_IF(upload_vec(p, &B.mtab, tab));
+        SPMV_RETURN_IF(plan_upload(p, &B.mtab, tab));
     }
     return bin_finish(p, p->n, L, o);
 }
 
-int build_bin_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, const double *d_val,
-                     const spmv_options_t &o) {
-    const int st = build_bin_device_impl(p, d_rp, d_col, d_val, o);
+int build_bin_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o) {
+    const int st = build_bin_device_impl(p, A, o);
     if (st != kBinNeedHostBuild) return st;
     // some row's column strips are out of order: sort every row's entries by
     // strip on the device (stable, so a strip's entries keep their CSR order
-    // -- the order the host fill reads them in) and build from that copy: the
-    // host builder's layout byte for byte.  No room for the copy: the caller
-    // stages the CSR through the host builder.
-    void *c2 = nullptr, *v2 = nullptr;
+    // -- the order the host fill reads them in) and build from that copy (the
+    // same row pointers): the host builder's layout byte for byte.  No room
+    // for the copy: the caller stages the CSR through the host builder.
+    DevScratch sc(p->stream);
+    int32_t *c2 = nullptr;
+    double *v2 = nullptr;
     const size_t nz = (size_t)std::max<int64_t>(p->nnz, 1);
-    if (hipMalloc(&c2, 4 * nz) != hipSuccess || hipMalloc(&v2, 8 * nz) != hipSuccess) {
-        (void)hipGetLastError();
-        if (c2) (void)hipFree(c2);
-        return kBinNeedHostBuild;
-    }
-    int st2 = bin_sort_rows_device(p, d_rp, d_col, d_val, (int32_t *)c2, (double *)v2);
-    if (st2 == SPMV_SUCCESS) st2 = build_bin_device_impl(p, d_rp, (const int32_t *)c2, (const double *)v2, o);
-    (void)hipStreamSynchronize(p->stream);
-    (void)hipFree(c2);
-    (void)hipFree(v2);
-    return st2;
+    if (sc.alloc(&c2, nz, "c2") != SPMV_SUCCESS || sc.alloc(&v2, nz, "v2") != SPMV_SUCCESS) return kBinNeedHostBuild;
+    SPMV_RETURN_IF(bin_sort_rows_device(p, A, c2, v2));
+    return build_bin_device_impl(p, DevCsr{A.m, A.n, A.nnz, A.h_rp, A.d_rp, c2, v2}, o);
 }
 
 }  // namespace spmv

@@ -30,24 +30,72 @@ static void stream_placement(spmv_plan_s *p, int fmt, const spmv_options_t &o) {
     if (const char *e = probe_env("SPMV_ARENA_VMM_MB")) p->arena.vmm_min = (size_t)std::max(0, std::atoi(e)) << 20;
 }
 
-static int check_device(int device) {
+// The prologue of every create path: resolve the plan's device (requested <
+// 0: the current one), check that it is a gfx950 and bind it.
+static int open_device(int requested, int *dev) {
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count == 0) {
         (void)hipGetLastError();
         set_error("no HIP device visible (libspmv_hip needs an MI355X / gfx950)");
         return SPMV_ERROR_NO_DEVICE;
     }
-    if (device >= count) {
+    *dev = requested;
+    if (*dev < 0) SPMV_HIP_TRY(hipGetDevice(dev));
+    if (*dev >= count) {
         set_error("device ordinal out of range");
         return SPMV_ERROR_INVALID_VALUE;
     }
     hipDeviceProp_t prop;
-    SPMV_HIP_TRY(hipGetDeviceProperties(&prop, device));
+    SPMV_HIP_TRY(hipGetDeviceProperties(&prop, *dev));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
         set_error(std::string("device is ") + prop.gcnArchName + "; kernels are built for gfx950 only");
         return SPMV_ERROR_NO_DEVICE;
     }
+    SPMV_HIP_TRY(hipSetDevice(*dev));
     return SPMV_SUCCESS;
+}
+
+// A fresh plan bound to `dev`; nullptr (error set) when the host is out of memory.
+static spmv_plan_s *new_plan(int dev, int64_t m, int64_t n, int64_t nnz) {
+    spmv_plan_s *p = new (std::nothrow) spmv_plan_s;
+    if (!p) {
+        set_error("host allocation of the plan failed");
+        return nullptr;
+    }
+    p->device = dev;
+    p->arena.device = dev;
+    if (const char *e = probe_env("SPMV_ARENA_VMM_MB")) p->arena.vmm_min = (size_t)std::max(0, std::atoi(e)) << 20;
+    p->m = m;
+    p->n = n;
+    p->nnz = nnz;
+    return p;
+}
+
+// The builders of every format, indexed by SPMV_FORMAT_* (AUTO is resolved
+// before the table is read).
+struct FormatBuilders {
+    int (*host)(spmv_plan_s *, const HostCsr &, const spmv_options_t &);
+    int (*device)(spmv_plan_s *, const DevCsr &, const spmv_options_t &);
+};
+static int build_ell_host(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o) {
+    return build_ell(p, A, o, INT32_MAX);
+}
+static const FormatBuilders kBuilders[SPMV_FORMAT_BIN + 1] = {
+    {nullptr, nullptr},                  // AUTO
+    {build_csr, build_csr_device},       // CSR
+    {build_ell_host, build_ell_device},  // ELL
+    {build_ss, build_ss_device},         // SS
+    {build_dia, build_dia_device},       // DIA
+    {build_hyb, build_hyb_device},       // HYB
+    {build_css, build_css_device},       // CSS
+    {build_coo, build_coo_device},       // COO
+    {build_jds, build_jds_device},       // JDS
+    {build_bin, build_bin_device},       // BIN
+};
+static const FormatBuilders *builders_for(int fmt) {
+    if (fmt > SPMV_FORMAT_AUTO && fmt <= SPMV_FORMAT_BIN) return &kBuilders[fmt];
+    set_error("unknown format");
+    return nullptr;
 }
 
 // Validate a host CSR before anything touches the GPU: an out-of-range
@@ -97,16 +145,8 @@ static int create_device_impl(int64_t m, int64_t n, int64_t nnz, const int64_t *
     SPMV_CHECK_ARG(m < (int64_t)INT32_MAX && n < (int64_t)INT32_MAX, "m and n must be < 2^31 (int32 column indices)");
     SPMV_CHECK_ARG(d_row_ptr != nullptr, "row_ptr is NULL");
     SPMV_CHECK_ARG(nnz == 0 || (d_col_idx != nullptr && d_val != nullptr), "col/val is NULL");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) {
-        (void)hipGetLastError();
-        set_error("no HIP device visible (libspmv_hip needs an MI355X / gfx950)");
-        return SPMV_ERROR_NO_DEVICE;
-    }
-    int dev = o.device;
-    if (dev < 0) SPMV_HIP_TRY(hipGetDevice(&dev));
-    SPMV_RETURN_IF(check_device(dev));
-    SPMV_HIP_TRY(hipSetDevice(dev));
+    int dev = -1;
+    SPMV_RETURN_IF(open_device(o.device, &dev));
     const void *ptrs[3] = {d_row_ptr, d_col_idx, d_val};
     for (int k = 0; k < (nnz ? 3 : 1); ++k) {
         hipPointerAttribute_t a;
@@ -117,24 +157,14 @@ static int create_device_impl(int64_t m, int64_t n, int64_t nnz, const int64_t *
         }
     }
     SPMV_RETURN_IF(validate_csr_device(d_row_ptr, m, d_col_idx, nnz, n));
-    spmv_plan_s *p = new (std::nothrow) spmv_plan_s;
-    if (!p) {
-        set_error("host allocation of the plan failed");
-        return SPMV_ERROR_OUT_OF_MEMORY;
-    }
-    p->device = dev;
-    p->arena.device = dev;
-    if (const char *e = probe_env("SPMV_ARENA_VMM_MB")) p->arena.vmm_min = (size_t)std::max(0, std::atoi(e)) << 20;
-    p->m = m;
-    p->n = n;
-    p->nnz = nnz;
+    spmv_plan_s *p = new_plan(dev, m, n, nnz);
+    if (!p) return SPMV_ERROR_OUT_OF_MEMORY;
     // the row pointers are the only part of the matrix the host sees: row
-    // lengths drive AUTO and every slice / bin / overflow decision
+    // lengths drive AUTO and every slice / bin / overflow decision (an explicit
+    // SS, DIA or COO request never reads them on the host and does not pay for
+    // the copy)
     std::vector<int64_t> hrp;
-    const bool need_rp = o.format == SPMV_FORMAT_AUTO || o.format == SPMV_FORMAT_ELL || o.format == SPMV_FORMAT_HYB ||
-                         o.format == SPMV_FORMAT_JDS || o.format == SPMV_FORMAT_CSS ||
-                         (o.format == SPMV_FORMAT_CSR && o.crs_exact);
-    if (need_rp) {
+    if (o.format != SPMV_FORMAT_SS && o.format != SPMV_FORMAT_DIA && o.format != SPMV_FORMAT_COO) {
         hrp.resize((size_t)m + 1);
         const hipError_t e = hipMemcpy(hrp.data(), d_row_ptr, 8 * (size_t)(m + 1), hipMemcpyDeviceToHost);
         if (e != hipSuccess) {
@@ -172,30 +202,16 @@ static int create_device_impl(int64_t m, int64_t n, int64_t nnz, const int64_t *
             });
         if (census != SPMV_SUCCESS && census != kDiaRefused) st = census;
     }
-    const double mean = m ? (double)nnz / (double)m : 0.0;
     bool host_build = false;
     if (st == SPMV_SUCCESS) {
         stream_placement(p, fmt, o);
-        switch (fmt) {
-            case SPMV_FORMAT_CSR: st = build_csr_device(p, d_row_ptr, d_col_idx, d_val, o, mean); break;
-            case SPMV_FORMAT_SS: st = build_ss_device(p, d_row_ptr, d_col_idx, d_val, o, mean); break;
-            case SPMV_FORMAT_DIA: st = build_dia_device(p, A, o); break;
-            case SPMV_FORMAT_ELL: st = build_ell_device(p, A, o); break;
-            case SPMV_FORMAT_HYB: st = build_hyb_device(p, A, o); break;
-            case SPMV_FORMAT_JDS: st = build_jds_device(p, A, o); break;
-            case SPMV_FORMAT_COO: st = build_coo_device(p, A, o); break;
-            case SPMV_FORMAT_BIN:
-                if (probe_env("SPMV_BIN_HOST_BUILD")) host_build = true;
-                else st = build_bin_device(p, d_row_ptr, d_col_idx, d_val, o);
-                // (kBinNeedHostBuild: rows out of strip order and no room
-                // for their sorted copy -- the host builder below)
-                if (st == kBinNeedHostBuild) host_build = true;
-                break;
-            case SPMV_FORMAT_CSS: st = build_css_device(p, A, o); break;
-            default:
-                set_error("unknown format");
-                st = SPMV_ERROR_INVALID_VALUE;
-        }
+        const FormatBuilders *b = builders_for(fmt);
+        if (!b) st = SPMV_ERROR_INVALID_VALUE;
+        else if (fmt == SPMV_FORMAT_BIN && probe_env("SPMV_BIN_HOST_BUILD")) host_build = true;
+        else st = b->device(p, A, o);
+        // (BIN: rows out of strip order and no room for their sorted copy --
+        // the host builder below)
+        if (st == kBinNeedHostBuild) host_build = true;
     }
     if (st == SPMV_SUCCESS && !host_build) {
         p->format = fmt;
@@ -278,16 +294,8 @@ static int create_from_csr(const HostCsr &A, const spmv_options_t *opt_in, spmv_
     else spmv_options_default(&o);
     SPMV_CHECK_ARG(o.build >= SPMV_BUILD_AUTO && o.build <= SPMV_BUILD_DEVICE, "build must be SPMV_BUILD_*");
     SPMV_RETURN_IF(validate_csr(A));
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) {
-        (void)hipGetLastError();
-        set_error("no HIP device visible (libspmv_hip needs an MI355X / gfx950)");
-        return SPMV_ERROR_NO_DEVICE;
-    }
-    int dev = o.device;
-    if (dev < 0) SPMV_HIP_TRY(hipGetDevice(&dev));
-    SPMV_RETURN_IF(check_device(dev));
-    SPMV_HIP_TRY(hipSetDevice(dev));
+    int dev = -1;
+    SPMV_RETURN_IF(open_device(o.device, &dev));
     // the device builders make every format; what they cannot (BIN rows out
     // of strip order without room for their sorted copy) and a staging copy
     // that does not fit take the host builders below -- with the format AUTO
@@ -299,35 +307,13 @@ static int create_from_csr(const HostCsr &A, const spmv_options_t *opt_in, spmv_
         if (st == kNeedHostBuild) o = ho;
         SPMV_HIP_TRY(hipSetDevice(dev));
     }
-    spmv_plan_s *p = new (std::nothrow) spmv_plan_s;
-    if (!p) {
-        set_error("host allocation of the plan failed");
-        return SPMV_ERROR_OUT_OF_MEMORY;
-    }
-    p->device = dev;
-    p->arena.device = dev;
-    if (const char *e = probe_env("SPMV_ARENA_VMM_MB")) p->arena.vmm_min = (size_t)std::max(0, std::atoi(e)) << 20;
-    p->m = A.m;
-    p->n = A.n;
-    p->nnz = A.nnz;
+    spmv_plan_s *p = new_plan(dev, A.m, A.n, A.nnz);
+    if (!p) return SPMV_ERROR_OUT_OF_MEMORY;
     int fmt = o.format == SPMV_FORMAT_AUTO ? choose_format(A, o) : o.format;
     if (fmt == SPMV_FORMAT_CSR && o.crs_exact) fmt = choose_crs_exact(A, o);
     stream_placement(p, fmt, o);
-    int st;
-    switch (fmt) {
-        case SPMV_FORMAT_CSR: st = build_csr(p, A, o); break;
-        case SPMV_FORMAT_ELL: st = build_ell(p, A, o, INT32_MAX); break;
-        case SPMV_FORMAT_HYB: st = build_hyb(p, A, o); break;
-        case SPMV_FORMAT_SS: st = build_ss(p, A, o); break;
-        case SPMV_FORMAT_DIA: st = build_dia(p, A, o); break;
-        case SPMV_FORMAT_CSS: st = build_css(p, A, o); break;
-        case SPMV_FORMAT_COO: st = build_coo(p, A, o); break;
-        case SPMV_FORMAT_JDS: st = build_jds(p, A, o); break;
-        case SPMV_FORMAT_BIN: st = build_bin(p, A, o); break;
-        default:
-            set_error("unknown format");
-            st = SPMV_ERROR_INVALID_VALUE;
-    }
+    const FormatBuilders *b = builders_for(fmt);
+    const int st = b ? b->host(p, A, o) : SPMV_ERROR_INVALID_VALUE;
     if (st != SPMV_SUCCESS) {
         p->arena.release();
         delete p;
@@ -411,16 +397,8 @@ int spmv_plan_create_csr32_device(int32_t m, int32_t n, int32_t nnz, const int32
     SPMV_CHECK_ARG(out != nullptr, "plan out-pointer is NULL");
     *out = nullptr;
     SPMV_CHECK_ARG(m >= 0 && n >= 0 && nnz >= 0 && d_row_ptr != nullptr, "bad dimensions or NULL row_ptr");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) {
-        (void)hipGetLastError();
-        set_error("no HIP device visible (libspmv_hip needs an MI355X / gfx950)");
-        return SPMV_ERROR_NO_DEVICE;
-    }
-    int dev = opt && opt->device >= 0 ? opt->device : -1;
-    if (dev < 0) SPMV_HIP_TRY(hipGetDevice(&dev));
-    SPMV_RETURN_IF(check_device(dev));
-    SPMV_HIP_TRY(hipSetDevice(dev));
+    int dev = -1;
+    SPMV_RETURN_IF(open_device(opt ? opt->device : -1, &dev));
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, d_row_ptr) != hipSuccess || a.type != hipMemoryTypeDevice || a.device != dev) {
         (void)hipGetLastError();
@@ -545,18 +523,20 @@ int spmv_fetch_y(spmv_plan_t p, double *y) {
 int spmv_time(spmv_plan_t p, const double *x_dev, double *y_dev, int32_t iters, double *ms) {
     SPMV_CHECK_ARG(p != nullptr && ms != nullptr && iters > 0, "bad arguments");
     SPMV_RETURN_IF(bind_device(p));
-    hipEvent_t a, b;
-    SPMV_HIP_TRY(hipEventCreate(&a));
-    SPMV_HIP_TRY(hipEventCreate(&b));
-    SPMV_HIP_TRY(hipEventRecord(a, p->stream));
+    // both events are destroyed on every path
+    hipEvent_t a = nullptr, b = nullptr;
+    hipError_t e = hipEventCreate(&a);
+    if (e == hipSuccess) e = hipEventCreate(&b);
+    if (e == hipSuccess) e = hipEventRecord(a, p->stream);
     int st = SPMV_SUCCESS;
-    for (int i = 0; i < iters && st == SPMV_SUCCESS; ++i) st = dispatch(p, x_dev, y_dev);
-    SPMV_HIP_TRY(hipEventRecord(b, p->stream));
-    SPMV_HIP_TRY(hipEventSynchronize(b));
+    for (int i = 0; i < iters && st == SPMV_SUCCESS && e == hipSuccess; ++i) st = dispatch(p, x_dev, y_dev);
+    if (e == hipSuccess) e = hipEventRecord(b, p->stream);
+    if (e == hipSuccess) e = hipEventSynchronize(b);
     float f = 0;
-    SPMV_HIP_TRY(hipEventElapsedTime(&f, a, b));
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
+    if (e == hipSuccess) e = hipEventElapsedTime(&f, a, b);
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+    SPMV_HIP_TRY(e);
     *ms = f;
     return st;
 }

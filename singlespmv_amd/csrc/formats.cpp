@@ -14,7 +14,7 @@
 #include <queue>
 #include <vector>
 
-#include "internal.hpp"
+#include "build_util.hpp"
 
 namespace spmv {
 
@@ -151,25 +151,6 @@ void DevArena::release() {
     bytes = 0;
 }
 
-// Allocate count+pad elements, copy count from host, zero the pad.
-template <typename T>
-static int upload(spmv_plan_s *p, T **dst, const T *src, int64_t count, int64_t pad = 0) {
-    void *q = nullptr;
-    SPMV_RETURN_IF(p->arena.alloc(&q, sizeof(T) * (size_t)(count + pad)));
-    if (count > 0) SPMV_HIP_TRY(hipMemcpy(q, src, sizeof(T) * (size_t)count, hipMemcpyHostToDevice));
-    if (pad > 0) SPMV_HIP_TRY(hipMemset((char *)q + sizeof(T) * count, 0, sizeof(T) * (size_t)pad));
-    *dst = (T *)q;
-    return SPMV_SUCCESS;
-}
-
-template <typename T>
-static int dev_alloc(spmv_plan_s *p, T **dst, int64_t count) {
-    void *q = nullptr;
-    SPMV_RETURN_IF(p->arena.alloc(&q, sizeof(T) * (size_t)count));
-    *dst = (T *)q;
-    return SPMV_SUCCESS;
-}
-
 static inline int64_t round_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
 int auto_csr_lanes(double mean_row) {
@@ -298,7 +279,7 @@ int csr_plan_lanes(spmv_plan_s *p, const int64_t *row_ptr, int64_t m, const spmv
     int64_t pos[kCsrBins];
     for (int b = 0; b < kCsrBins; ++b) pos[b] = c.bin_off[b];
     for (int64_t r = 0; r < m; ++r) rows[(size_t)pos[bin[(size_t)r]]++] = (int32_t)r;
-    return upload(p, &c.bin_rows, rows.data(), m);
+    return plan_upload(p, &c.bin_rows, rows.data(), m);
 }
 
 // x windows of csr_slabx's workgroups (k_csr.hip): the column span of each
@@ -330,7 +311,7 @@ int csr_windows_finish(spmv_plan_s *p, const std::vector<int32_t> &lo, const std
     std::vector<int32_t> w0(lo);
     for (int64_t g = 0; g < ng; ++g)
         if (hi[(size_t)g] < 0) w0[(size_t)g] = std::numeric_limits<int32_t>::max();  // empty: no lower bound
-    return upload(p, &c.win0, w0.data(), ng);
+    return plan_upload(p, &c.win0, w0.data(), ng);
 }
 
 static int csr_x_windows(spmv_plan_s *p, const HostCsr &A) {
@@ -357,14 +338,14 @@ int build_csr(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o) {
     // exercises that kernel instance on small matrices in the tests
     c.rp64 = A.nnz >= (int64_t)std::numeric_limits<int32_t>::max() - 64 || o.csr_row_ptr64 != 0 || probe_env("SPMV_CSR_FORCE_RP64");
     if (c.rp64) {
-        SPMV_RETURN_IF(upload(p, (int64_t **)&c.row_ptr, A.row_ptr, A.m + 1));
+        SPMV_RETURN_IF(plan_upload(p, (int64_t **)&c.row_ptr, A.row_ptr, A.m + 1));
     } else {
         std::vector<int32_t> rp32((size_t)A.m + 1);
 #pragma omp parallel for schedule(static)
         for (int64_t i = 0; i <= A.m; ++i) rp32[i] = (int32_t)A.row_ptr[i];
-        SPMV_RETURN_IF(upload(p, (int32_t **)&c.row_ptr, rp32.data(), A.m + 1));
+        SPMV_RETURN_IF(plan_upload(p, (int32_t **)&c.row_ptr, rp32.data(), A.m + 1));
     }
-    SPMV_RETURN_IF(upload(p, &c.col, A.col, A.nnz, kPad));
+    SPMV_RETURN_IF(plan_upload(p, &c.col, A.col, A.nnz, kPad));
     SPMV_RETURN_IF(csr_plan_lanes(p, A.row_ptr, A.m, o));
     c.val_halves = csr_val_halves_wanted(c);
     if (c.val_halves) {
@@ -375,9 +356,9 @@ int build_csr(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o) {
             const int64_t e = csr_val_halves_entry(pos);
             vh[(size_t)pos] = e < A.nnz ? A.val[e] : 0.0;
         }
-        SPMV_RETURN_IF(upload(p, &c.val, vh.data(), total, kPad));
+        SPMV_RETURN_IF(plan_upload(p, &c.val, vh.data(), total, kPad));
     } else {
-        SPMV_RETURN_IF(upload(p, &c.val, A.val, A.nnz, kPad));
+        SPMV_RETURN_IF(plan_upload(p, &c.val, A.val, A.nnz, kPad));
     }
     if (c.lanes > 0) SPMV_RETURN_IF(csr_x_windows(p, A));
     csr_finish_info(p);
@@ -458,9 +439,9 @@ int build_ell(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &, int cap,
             }
         }
     }
-    SPMV_RETURN_IF(upload(p, &e.slice_off, off.data(), e.n_slices + 1));
-    SPMV_RETURN_IF(upload(p, &e.col, col.data(), total));
-    SPMV_RETURN_IF(upload(p, &e.val, val.data(), total));
+    SPMV_RETURN_IF(plan_upload(p, &e.slice_off, off.data(), e.n_slices + 1));
+    SPMV_RETURN_IF(plan_upload(p, &e.col, col.data(), total));
+    SPMV_RETURN_IF(plan_upload(p, &e.val, val.data(), total));
     ell_finish_info(p, maxw, total);
     return SPMV_SUCCESS;
 }
@@ -486,11 +467,11 @@ int overflow_upload_index(spmv_plan_s *p, const std::vector<int32_t> &rows, cons
     HybDev &h = p->hyb;
     h.n_rows = (int64_t)rows.size();
     h.nnz = rp.back();
-    SPMV_RETURN_IF(upload(p, &h.rows, rows.data(), h.n_rows));
-    SPMV_RETURN_IF(upload(p, &h.row_ptr, rp.data(), h.n_rows + 1));
+    SPMV_RETURN_IF(plan_upload(p, &h.rows, rows.data(), h.n_rows));
+    SPMV_RETURN_IF(plan_upload(p, &h.row_ptr, rp.data(), h.n_rows + 1));
     std::vector<int32_t> binned;
     csr_bin_rows(rp.data(), h.n_rows, binned, h.bin_off);
-    return upload(p, &h.bin_rows, binned.data(), h.n_rows);
+    return plan_upload(p, &h.bin_rows, binned.data(), h.n_rows);
 }
 
 static int build_overflow(spmv_plan_s *p, const HostCsr &A, int K) {
@@ -510,8 +491,8 @@ static int build_overflow(spmv_plan_s *p, const HostCsr &A, int K) {
     }
     // overflow rows binned by overflow length (adaptive kernel, y +=)
     SPMV_RETURN_IF(overflow_upload_index(p, rows, rp));
-    SPMV_RETURN_IF(upload(p, &h.col, col.data(), h.nnz, kPad));
-    SPMV_RETURN_IF(upload(p, &h.val, val.data(), h.nnz, kPad));
+    SPMV_RETURN_IF(plan_upload(p, &h.col, col.data(), h.nnz, kPad));
+    SPMV_RETURN_IF(plan_upload(p, &h.val, val.data(), h.nnz, kPad));
     return SPMV_SUCCESS;
 }
 
@@ -571,7 +552,7 @@ int build_jds(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o) {
     const bool identity = jds_layout(A.row_ptr, A.m, A.nnz, o, order, &K);
     SPMV_RETURN_IF(build_ell(p, A, o, K, identity ? nullptr : order.data()));
     const int64_t ell_slots = p->stored_slots;
-    if (!identity) SPMV_RETURN_IF(upload(p, &p->ell.perm, order.data(), A.m));
+    if (!identity) SPMV_RETURN_IF(plan_upload(p, &p->ell.perm, order.data(), A.m));
     SPMV_RETURN_IF(build_overflow(p, A, K));
     jds_finish_info(p, identity, ell_slots);
     return SPMV_SUCCESS;
@@ -590,9 +571,9 @@ int build_coo(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &) {
 #pragma omp parallel for schedule(dynamic, 1024)
     for (int64_t r = 0; r < A.m; ++r)
         for (int64_t j = A.row_ptr[r]; j < A.row_ptr[r + 1]; ++j) row[(size_t)j] = (int32_t)r;
-    SPMV_RETURN_IF(upload(p, &c.row, row.data(), total));
-    SPMV_RETURN_IF(upload(p, &c.col, A.col, A.nnz, total - A.nnz));
-    SPMV_RETURN_IF(upload(p, &c.val, A.val, A.nnz, total - A.nnz));
+    SPMV_RETURN_IF(plan_upload(p, &c.row, row.data(), total));
+    SPMV_RETURN_IF(plan_upload(p, &c.col, A.col, A.nnz, total - A.nnz));
+    SPMV_RETURN_IF(plan_upload(p, &c.val, A.val, A.nnz, total - A.nnz));
     coo_finish_info(p);
     return SPMV_SUCCESS;
 }
@@ -705,8 +686,8 @@ int build_ss(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o) {
             if (A.row_ptr[r + 1] > A.row_ptr[r]) nzrow[a++] = (int32_t)r;
             else empty[b++] = (int32_t)r;
         }
-        SPMV_RETURN_IF(upload(p, &s.nzrow, nzrow.data(), s.n_nonempty));
-        SPMV_RETURN_IF(upload(p, &s.empty_rows, empty.data(), s.n_empty));
+        SPMV_RETURN_IF(plan_upload(p, &s.nzrow, nzrow.data(), s.n_nonempty));
+        SPMV_RETURN_IF(plan_upload(p, &s.empty_rows, empty.data(), s.n_empty));
     }
     const int64_t total = s.n_tiles * T;
     std::vector<uint32_t> flags((size_t)s.n_tiles * 64 * W, 0u);
@@ -740,13 +721,13 @@ int build_ss(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o) {
     }
     std::vector<int32_t> win;
     ss_tile_windows(A.col, A.nnz, s.n_tiles, s.sigma, win);
-    SPMV_RETURN_IF(upload(p, &s.col, col.data(), total));
-    SPMV_RETURN_IF(upload(p, &s.val, val.data(), total));
-    SPMV_RETURN_IF(upload(p, &s.flags, flags.data(), s.n_tiles * 64 * W));
-    SPMV_RETURN_IF(upload(p, &s.tile_ord, tord.data(), s.n_tiles));
-    SPMV_RETURN_IF(upload(p, &s.win, win.data(), 2 * s.n_tiles));
-    SPMV_RETURN_IF(dev_alloc(p, &s.ht, 2 * s.n_tiles));
-    SPMV_RETURN_IF(dev_alloc(p, &s.tail_ord, s.n_tiles));
+    SPMV_RETURN_IF(plan_upload(p, &s.col, col.data(), total));
+    SPMV_RETURN_IF(plan_upload(p, &s.val, val.data(), total));
+    SPMV_RETURN_IF(plan_upload(p, &s.flags, flags.data(), s.n_tiles * 64 * W));
+    SPMV_RETURN_IF(plan_upload(p, &s.tile_ord, tord.data(), s.n_tiles));
+    SPMV_RETURN_IF(plan_upload(p, &s.win, win.data(), 2 * s.n_tiles));
+    SPMV_RETURN_IF(plan_alloc(p, &s.ht, 2 * s.n_tiles));
+    SPMV_RETURN_IF(plan_alloc(p, &s.tail_ord, s.n_tiles));
     SPMV_RETURN_IF(ss_plan_tail_ord(p));
     ss_finish_info(p);
     return SPMV_SUCCESS;
@@ -932,7 +913,7 @@ int build_dia(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o) {
             }
             val[(size_t)at] += A.val[j];  // duplicates are summed
         }
-    SPMV_RETURN_IF(upload(p, &d.off, offs.data(), d.n_diags));
+    SPMV_RETURN_IF(plan_upload(p, &d.off, offs.data(), d.n_diags));
     if (const char *e = probe_env("SPMV_DIA_DEBUG")) d.dbg = std::atoi(e);
     if (const char *e = probe_env("SPMV_DIA_LDS_KB")) d.lds_kb = std::atoi(e);
     p->stored_slots = slots;
@@ -952,7 +933,7 @@ int build_dia(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o) {
         d.val = (double *)q;
         d.placement = SPMV_PLACEMENT_VMM;
     } else {
-        SPMV_RETURN_IF(upload(p, &d.val, val.data(), slots));
+        SPMV_RETURN_IF(plan_upload(p, &d.val, val.data(), slots));
         SPMV_RETURN_IF(dia_placement(p, A.m, A.n, vbytes, oo));
     }
     dia_finish_info(p);
@@ -1235,32 +1216,32 @@ int css_fill_host(spmv_plan_s *p, const HostCsr &A, CssLayout &CL) {
     }
     // +256 entries: a contiguous list's last chunk may read past the array
     // (masked lanes); zero col, val -- and slot 0, which masking overrides
-    SPMV_RETURN_IF(upload(p, &c.col, col.data(), total, 256));
-    SPMV_RETURN_IF(upload(p, &c.row, slot.data(), total, 256));
-    SPMV_RETURN_IF(upload(p, &c.val, val.data(), total, 256));
+    SPMV_RETURN_IF(plan_upload(p, &c.col, col.data(), total, 256));
+    SPMV_RETURN_IF(plan_upload(p, &c.row, slot.data(), total, 256));
+    SPMV_RETURN_IF(plan_upload(p, &c.val, val.data(), total, 256));
     return SPMV_SUCCESS;
 }
 
 // the layout's host arrays, pacing counters and plan info (both builders)
 int css_finish(spmv_plan_s *p, const CssLayout &CL, int64_t m, int64_t n, int64_t nnz) {
     CssDev &c = p->css;
-    SPMV_RETURN_IF(upload(p, &c.woff, CL.woff.data(), CL.nlists + 1));
-    SPMV_RETURN_IF(upload(p, &c.wlen, CL.wlen.data(), CL.nlists));
-    SPMV_RETURN_IF(upload(p, &c.bstart, CL.roff.data(), CL.nblocks + 1));
+    SPMV_RETURN_IF(plan_upload(p, &c.woff, CL.woff.data(), CL.nlists + 1));
+    SPMV_RETURN_IF(plan_upload(p, &c.wlen, CL.wlen.data(), CL.nlists));
+    SPMV_RETURN_IF(plan_upload(p, &c.bstart, CL.roff.data(), CL.nblocks + 1));
     c.rmap = nullptr;  // identity (rows in matrix order) unless long rows were dealt out
     c.n_rmap = 0;
     if (CL.has_longs) {
-        SPMV_RETURN_IF(upload(p, &c.rmap, CL.rmap.data(), (int64_t)CL.rmap.size()));
+        SPMV_RETURN_IF(plan_upload(p, &c.rmap, CL.rmap.data(), (int64_t)CL.rmap.size()));
         c.n_rmap = (int64_t)CL.rmap.size();
     }
-    SPMV_RETURN_IF(upload(p, &c.moff, CL.moff.data(), CL.nblocks + 1));
-    SPMV_RETURN_IF(upload(p, &c.merge, CL.merge.data(), 3 * CL.moff[(size_t)CL.nblocks]));
+    SPMV_RETURN_IF(plan_upload(p, &c.moff, CL.moff.data(), CL.nblocks + 1));
+    SPMV_RETURN_IF(plan_upload(p, &c.merge, CL.merge.data(), 3 * CL.moff[(size_t)CL.nblocks]));
     std::vector<uint64_t> zeros(8 * 16, 0);
-    SPMV_RETURN_IF(upload(p, &c.prog, zeros.data(), (int64_t)zeros.size()));
+    SPMV_RETURN_IF(plan_upload(p, &c.prog, zeros.data(), (int64_t)zeros.size()));
     c.launches = 0;
     c.n_lists = CL.nlists;
     if (const char *d = probe_env("SPMV_CSS_DEBUG")) c.dbg = std::atoi(d);
-    if (c.dbg & 32) SPMV_RETURN_IF(dev_alloc(p, &c.tstamp, (int64_t)c.P * c.nwg * (kCssWorkers + 2)));
+    if (c.dbg & 32) SPMV_RETURN_IF(plan_alloc(p, &c.tstamp, (int64_t)c.P * c.nwg * (kCssWorkers + 2)));
     p->stored_slots = CL.total;
     p->algo_bytes = 12 * nnz + 8 * n + 8 * m;
     p->n_kernels = 1;

@@ -473,26 +473,61 @@ int build_css(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o);
 int build_coo(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o);
 int build_jds(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o);
 int build_bin(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o);  // build_bin.cpp
+
+// A CSR that already lives in HBM, handed to the device builders (k_convert,
+// k_devbuild, k_css_build, k_bin_build): only the row pointers visit the host
+// (layout decisions); entries move HBM -> HBM.
+struct DevCsr {
+    int64_t m, n, nnz;
+    const int64_t *h_rp;  // host copy of the row pointers (null for SS, DIA and COO, which never read them)
+    const int64_t *d_rp;
+    const int32_t *d_col;
+    const double *d_val;
+};
+
+// BIN host-side layout shared by the host and the device builder
+// (build_bin.cpp) and the device fill (k_bin_build.hip).
+struct BinLayout {
+    int64_t S = 0, NB = 0, E = 0, PAD = 16;
+    std::vector<int32_t> row0;          // [NB + 1]
+    std::vector<int32_t> cnt;           // [NB * S] entries per (bin, strip)
+    std::vector<int64_t> off1, off2;    // [NB * S] segment start, Mul / Sum order
+    std::vector<int64_t> run_off;       // [NBK * NB + 1]
+    std::vector<int64_t> srun_off;      // [NBK * NB + 1] slot runs, each padded to 64*sum_u
+    int64_t ES = 0, SB = 1;             // slot entries; strips per block
+    std::vector<int64_t> strip_start;   // [G * (S + 1)] Mul-order start of (group, strip)
+    std::vector<int64_t> mul_bins;      // [NB] bins in Mul visiting order within each strip (per group)
+    // long rows (BinDev, the run path); LL = 0: none
+    int64_t LL = 0, NP = 0, E1 = 0, TRASH = 0;
+    std::vector<int64_t> eff_rp;        // [m + 1] cumulative Sum entries per row (bin cut)
+    std::vector<int64_t> lb_off;        // [S + 1] long entries of strip t in lb_j / lb_row
+    std::vector<int64_t> lb_j;          // entry index, ordered [strip][row][CSR order]
+    std::vector<int32_t> lb_row;
+    std::vector<int32_t> lpc;           // [NB * S] run pieces of (bin, strip)
+    std::vector<int64_t> lpoff;         // [NB * S] product position of (bin, strip)'s first piece
+    std::vector<int64_t> lpad;          // [S] long entries of strip t, padded to 64
+    std::vector<int64_t> lstart;        // [S] Mul position of strip t's first long block
+    std::vector<int64_t> lcode_off;     // [S] lcode index of the same
+    int64_t rpad(int64_t v) const { return (v + PAD - 1) & ~(PAD - 1); }
+    bool is_long(const int64_t *rp, int64_t r) const { return LL > 0 && rp[r + 1] - rp[r] >= LL; }
+};
 // BIN from a device CSR (build_bin.cpp + k_bin_build.hip), long rows
 // included; rows whose column strips are out of order are first sorted by
 // strip on the device (bin_sort_rows_device).  kBinNeedHostBuild is then
 // internal to the builder.
 constexpr int kBinNeedHostBuild = -1000;
-int build_bin_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, const double *d_val,
-                     const spmv_options_t &o);
-// k_bin_build.hip: bstart[b] = row_ptr[row0[b]] (first entry of each bin)
-// rows whose column strips are out of order: col2 / val2 (nnz each, the
-// caller's) = the CSR's entries stably sorted by strip inside every row
-int bin_sort_rows_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, const double *d_val,
-                         int32_t *col2, double *val2);
-// LL > 0: rows of >= LL entries take the run path and stay out of the segments
-int bin_count_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, const std::vector<int32_t> &row0,
+int build_bin_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o);
+// k_bin_build.hip: rows whose column strips are out of order: col2 / val2
+// (nnz each, the caller's) = the CSR's entries stably sorted by strip inside
+// every row
+int bin_sort_rows_device(spmv_plan_s *p, const DevCsr &A, int32_t *col2, double *val2);
+// entries per (bin, strip); bstart[b] = row_ptr[row0[b]] (first entry of each
+// bin); LL > 0: rows of >= LL entries take the run path and stay out of the segments
+int bin_count_device(spmv_plan_s *p, const DevCsr &A, const std::vector<int32_t> &row0,
                      const std::vector<int64_t> &bstart, int64_t S, int64_t LL, std::vector<int32_t> &cnt);
-int bin_fill_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, const double *d_val,
-                    const std::vector<int32_t> &row0, const std::vector<int64_t> &bstart,
-                    const std::vector<int32_t> &cnt, const std::vector<int64_t> &off1,
-                    const std::vector<int64_t> &off2, const std::vector<int64_t> &run_off,
-                    const std::vector<int64_t> &srun_off, int64_t S, int64_t E, int64_t ES, int64_t LL, int64_t E1,
+// the segments' entry arrays (L.LL as the caller's layout loop left it);
+// dst_fill: the trash line's destination group
+int bin_fill_device(spmv_plan_s *p, const DevCsr &A, const BinLayout &L, const std::vector<int64_t> &bstart,
                     int32_t dst_fill);
 // Long rows from a device CSR: each run is one long row's entries in one
 // strip (contiguous, the row's strips being non-decreasing).  The runs'
@@ -504,22 +539,15 @@ struct BinLongRuns {
     std::vector<int64_t> j0, q0, fpos;
     std::vector<int32_t> len, strip, slot, bin;
 };
-int bin_long_runs_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, const std::vector<int32_t> &lrows,
+int bin_long_runs_device(spmv_plan_s *p, const DevCsr &A, const std::vector<int32_t> &lrows,
                          std::vector<int64_t> &roff, std::vector<int32_t> &rstrip, std::vector<int64_t> &rbeg);
-int bin_long_fill_device(spmv_plan_s *p, const int32_t *d_col, const double *d_val, const BinLongRuns &LR,
-                         const std::vector<int64_t> &lb_off, const std::vector<int64_t> &lpad,
-                         const std::vector<int64_t> &lstart, const std::vector<int64_t> &lcode_off,
-                         const std::vector<int64_t> &run_off, const std::vector<int64_t> &srun_off, int64_t lrun0,
-                         int64_t trash);
+int bin_long_fill_device(spmv_plan_s *p, const DevCsr &A, const BinLayout &L, const BinLongRuns &LR, int64_t lrun0);
 // k_convert.hip -- device-input builders (the CSR already lives in HBM).
 int validate_csr_device(const int64_t *d_rp, int64_t m, const int32_t *d_col, int64_t nnz, int64_t n);
 int widen_row_ptr_device(const int32_t *d_rp32, int64_t m, int64_t **d_rp64);  // hipMalloc'd; caller frees
 int launch_scale(const spmv_plan_s *p, double *y, double alpha);              // y *= alpha on p->stream
-int exclusive_scan_i64(const int64_t *in, int64_t *out, int64_t n, hipStream_t st, std::vector<void *> &tmp);
-int build_csr_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, const double *d_val,
-                     const spmv_options_t &o, double mean_row);
-int build_ss_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, const double *d_val,
-                    const spmv_options_t &o, double mean_row);
+int build_csr_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o);
+int build_ss_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o);
 int choose_format(const HostCsr &A, const spmv_options_t &o);
 int choose_format_rp(int64_t m, int64_t n, int64_t nnz, const int64_t *row_ptr, const spmv_options_t &o,
                      const std::function<bool()> &dia_ok);
@@ -540,15 +568,7 @@ void hyb_finish_info(spmv_plan_s *p, int K, int64_t ell_slots);
 void coo_finish_info(spmv_plan_s *p);
 void dia_finish_info(spmv_plan_s *p);
 int dia_placement(spmv_plan_s *p, int64_t m, int64_t n, size_t bytes, const spmv_options_t &o);
-// k_devbuild.hip -- the other formats from a device CSR (f2): only the row
-// pointers visit the host (layout decisions); entries move HBM -> HBM.
-struct DevCsr {
-    int64_t m, n, nnz;
-    const int64_t *h_rp;  // host copy of the row pointers
-    const int64_t *d_rp;
-    const int32_t *d_col;
-    const double *d_val;
-};
+// k_devbuild.hip -- the other formats from a device CSR (f2).
 constexpr int kDiaRefused = -1001;  // dia_offsets_device: too many diagonals / too much fill
 int dia_offsets_device(spmv_plan_s *p, const DevCsr &A, int max_diags, double max_fill, std::vector<int32_t> &offs);
 int build_dia_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o);

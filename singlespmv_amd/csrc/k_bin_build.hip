@@ -26,14 +26,12 @@
 #include <algorithm>
 #include <vector>
 
+#include "build_util.hpp"
 #include "device.hpp"
-#include "internal.hpp"
 
 namespace spmv {
 
 namespace {
-
-inline unsigned grid_of(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 65536)); }
 
 // first index i in [lo, hi) with a[i] > v (a non-decreasing)
 __device__ __forceinline__ int64_t upper_idx(const int64_t *__restrict__ a, int64_t lo, int64_t hi, int64_t v) {
@@ -262,44 +260,6 @@ __global__ __launch_bounds__(256) void bin_long_pad_kernel(int64_t S, const int6
             lcode[lcode_off[t] + p2] = (int32_t)(0x80000000u | (uint32_t)trash);
 }
 
-// hipMalloc'd scratch, freed (after the stream drains) on every exit path
-struct Scratch {
-    hipStream_t st;
-    std::vector<void *> v;
-    ~Scratch() {
-        (void)hipStreamSynchronize(st);
-        for (void *t : v) (void)hipFree(t);
-    }
-    template <typename T>
-    int alloc(T **q, size_t count) {
-        void *t = nullptr;
-        if (hipMalloc(&t, sizeof(T) * std::max<size_t>(count, 1)) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("BIN device build: scratch allocation failed");
-            return SPMV_ERROR_OUT_OF_MEMORY;
-        }
-        v.push_back(t);
-        *q = (T *)t;
-        return SPMV_SUCCESS;
-    }
-    template <typename T>
-    int upload(T **q, const std::vector<T> &h) {
-        SPMV_RETURN_IF(alloc(q, h.size()));
-        if (!h.empty()) SPMV_HIP_TRY(hipMemcpyAsync(*q, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, st));
-        return SPMV_SUCCESS;
-    }
-};
-
-int finish(hipStream_t st, const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        set_error(std::string("BIN device build (") + what + "): " + hipGetErrorString(e));
-        return SPMV_ERROR_HIP;
-    }
-    return SPMV_SUCCESS;
-}
-
 struct SortPlaceArgs {
     const int64_t *rp;
     const int32_t *col;
@@ -312,7 +272,7 @@ struct SortPlaceArgs {
 
 // keys, stable radix sort (the keys' significant bits only), placement
 template <typename K, typename V>
-int bin_sort_place(spmv_plan_s *p, Scratch &sc, const SortPlaceArgs &A) {
+int bin_sort_place(spmv_plan_s *p, DevScratch &sc, const SortPlaceArgs &A) {
     BinDev &B = p->bin;
     const hipStream_t st = p->stream;
     const int64_t nnz = p->nnz;
@@ -321,11 +281,11 @@ int bin_sort_place(spmv_plan_s *p, Scratch &sc, const SortPlaceArgs &A) {
     const K none = bits >= 64 ? (K)~0ull : (K)(((uint64_t)1 << bits) - 1);
     K *k0, *k1;
     V *v0, *v1;
-    SPMV_RETURN_IF(sc.alloc(&k0, (size_t)nnz));
-    SPMV_RETURN_IF(sc.alloc(&k1, (size_t)nnz));
-    SPMV_RETURN_IF(sc.alloc(&v0, (size_t)nnz));
-    SPMV_RETURN_IF(sc.alloc(&v1, (size_t)nnz));
-    const unsigned grid = grid_of(nnz);
+    SPMV_RETURN_IF(sc.alloc(&k0, (size_t)nnz, "BIN sort keys"));
+    SPMV_RETURN_IF(sc.alloc(&k1, (size_t)nnz, "BIN sort keys"));
+    SPMV_RETURN_IF(sc.alloc(&v0, (size_t)nnz, "BIN sort values"));
+    SPMV_RETURN_IF(sc.alloc(&v1, (size_t)nnz, "BIN sort values"));
+    const unsigned grid = grid_for(nnz);
     hipLaunchKernelGGL((bin_key_kernel<K, V>), dim3(grid), dim3(256), 0, st, A.rp, A.col, nnz, A.bstart, A.NB, A.row0,
                        (int32_t)B.strip, A.S, A.off2, A.LL, none, k0, v0);
     hipcub::DoubleBuffer<K> dk(k0, k1);
@@ -333,9 +293,9 @@ int bin_sort_place(spmv_plan_s *p, Scratch &sc, const SortPlaceArgs &A) {
     size_t tb = 0;
     SPMV_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dk, dv, nnz, 0, bits, st));
     char *tmp = nullptr;
-    SPMV_RETURN_IF(sc.alloc(&tmp, tb));
+    SPMV_RETURN_IF(sc.alloc(&tmp, tb, "BIN sort workspace"));
     SPMV_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, dk, dv, nnz, 0, bits, st));
-    hipLaunchKernelGGL((bin_place_kernel<V>), dim3(grid_of(A.n_seg)), dim3(256), 0, st, A.rp, A.col, A.val,
+    hipLaunchKernelGGL((bin_place_kernel<V>), dim3(grid_for(A.n_seg)), dim3(256), 0, st, A.rp, A.col, A.val,
                        (const V *)dv.Current(), A.n_seg, A.bstart, A.NB, A.row0, (int32_t)B.strip, A.S, A.off1, A.off2,
                        A.cbase, A.pbb, B.pad_log, A.run, A.srun, B.strip_block, B.sum_u, B.val1, B.cs1, B.slot2,
                        B.dst1);
@@ -343,51 +303,51 @@ int bin_sort_place(spmv_plan_s *p, Scratch &sc, const SortPlaceArgs &A) {
 }
 
 template <typename V>
-int bin_sort_rows_t(spmv_plan_s *p, Scratch &sc, const int64_t *d_rp, const int32_t *d_col, const double *d_val,
-                    int32_t *col2, double *val2) {
+int bin_sort_rows_t(spmv_plan_s *p, const DevCsr &A, int32_t *col2, double *val2) {
     const hipStream_t st = p->stream;
+    DevScratch sc(st);
     const int64_t m = p->m, nnz = p->nnz, C = p->bin.strip, S = std::max<int64_t>(1, (p->n + C - 1) / C);
     int bits = 1;
     while (bits < 64 && (((uint64_t)1 << bits) - 1) < (uint64_t)m * (uint64_t)S) ++bits;
     uint64_t *k0, *k1;
     V *v0, *v1;
-    SPMV_RETURN_IF(sc.alloc(&k0, (size_t)nnz));
-    SPMV_RETURN_IF(sc.alloc(&k1, (size_t)nnz));
-    SPMV_RETURN_IF(sc.alloc(&v0, (size_t)nnz));
-    SPMV_RETURN_IF(sc.alloc(&v1, (size_t)nnz));
-    hipLaunchKernelGGL((bin_row_strip_key_kernel<V>), dim3(grid_of(nnz)), dim3(256), 0, st, d_rp, m, d_col, nnz,
+    SPMV_RETURN_IF(sc.alloc(&k0, (size_t)nnz, "BIN sort keys"));
+    SPMV_RETURN_IF(sc.alloc(&k1, (size_t)nnz, "BIN sort keys"));
+    SPMV_RETURN_IF(sc.alloc(&v0, (size_t)nnz, "BIN sort values"));
+    SPMV_RETURN_IF(sc.alloc(&v1, (size_t)nnz, "BIN sort values"));
+    hipLaunchKernelGGL((bin_row_strip_key_kernel<V>), dim3(grid_for(nnz)), dim3(256), 0, st, A.d_rp, m, A.d_col, nnz,
                        (int32_t)C, S, k0, v0);
     hipcub::DoubleBuffer<uint64_t> dk(k0, k1);
     hipcub::DoubleBuffer<V> dv(v0, v1);
     size_t tb = 0;
     SPMV_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dk, dv, nnz, 0, bits, st));
     char *tmp = nullptr;
-    SPMV_RETURN_IF(sc.alloc(&tmp, tb));
+    SPMV_RETURN_IF(sc.alloc(&tmp, tb, "BIN sort workspace"));
     SPMV_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, dk, dv, nnz, 0, bits, st));
-    hipLaunchKernelGGL((bin_gather_entries_kernel<V>), dim3(grid_of(nnz)), dim3(256), 0, st, (const V *)dv.Current(),
-                       nnz, d_col, d_val, col2, val2);
-    return finish(st, "row strip sort");
+    hipLaunchKernelGGL((bin_gather_entries_kernel<V>), dim3(grid_for(nnz)), dim3(256), 0, st, (const V *)dv.Current(),
+                       nnz, A.d_col, A.d_val, col2, val2);
+    return build_sync(st, "BIN device build (row strip sort)");
 }
 
 }  // namespace
 
-int bin_count_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, const std::vector<int32_t> &row0,
+int bin_count_device(spmv_plan_s *p, const DevCsr &A, const std::vector<int32_t> &row0,
                      const std::vector<int64_t> &bstart, int64_t S, int64_t LL, std::vector<int32_t> &cnt) {
     const hipStream_t st = p->stream;
     const int64_t NB = (int64_t)row0.size() - 1;
-    Scratch sc{st, {}};
+    DevScratch sc(st);
     int32_t *d_row0, *d_cnt;
     int64_t *d_bstart;
     unsigned *d_bad;
     SPMV_RETURN_IF(sc.upload(&d_row0, row0));
     SPMV_RETURN_IF(sc.upload(&d_bstart, bstart));
-    SPMV_RETURN_IF(sc.alloc(&d_cnt, (size_t)(NB * S)));
-    SPMV_RETURN_IF(sc.alloc(&d_bad, 1));
+    SPMV_RETURN_IF(sc.alloc(&d_cnt, (size_t)(NB * S), "BIN counts"));
+    SPMV_RETURN_IF(sc.alloc(&d_bad, 1, "bad"));
     SPMV_HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * (size_t)(NB * S), st));
     SPMV_HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(unsigned), st));
-    hipLaunchKernelGGL(bin_count_kernel, dim3(grid_of(p->nnz)), dim3(256), 0, st, d_rp, d_col, p->nnz, d_bstart, NB,
+    hipLaunchKernelGGL(bin_count_kernel, dim3(grid_for(p->nnz)), dim3(256), 0, st, A.d_rp, A.d_col, p->nnz, d_bstart, NB,
                        d_row0, (int32_t)p->bin.strip, S, LL, d_cnt, d_bad);
-    SPMV_RETURN_IF(finish(st, "counts"));
+    SPMV_RETURN_IF(build_sync(st, "BIN device build (counts)"));
     unsigned bad = 0;
     cnt.assign((size_t)(NB * S), 0);
     SPMV_HIP_TRY(hipMemcpy(cnt.data(), d_cnt, sizeof(int32_t) * cnt.size(), hipMemcpyDeviceToHost));
@@ -395,22 +355,17 @@ int bin_count_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, 
     return bad ? kBinNeedHostBuild : SPMV_SUCCESS;
 }
 
-int bin_fill_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, const double *d_val,
-                    const std::vector<int32_t> &row0, const std::vector<int64_t> &bstart,
-                    const std::vector<int32_t> &cnt, const std::vector<int64_t> &off1,
-                    const std::vector<int64_t> &off2, const std::vector<int64_t> &run_off,
-                    const std::vector<int64_t> &srun_off, int64_t S, int64_t E, int64_t ES, int64_t LL, int64_t E1,
+int bin_fill_device(spmv_plan_s *p, const DevCsr &A, const BinLayout &L, const std::vector<int64_t> &bstart,
                     int32_t dst_fill) {
     BinDev &B = p->bin;
     const hipStream_t st = p->stream;
-    const int64_t NB = (int64_t)row0.size() - 1, C = B.strip;
+    const int64_t NB = (int64_t)L.row0.size() - 1, S = L.S, E = L.E, ES = L.ES, LL = L.LL, E1 = L.E1;
     // product offset of each bin's row group (nonzero only when groups
     // re-use one product buffer)
     std::vector<int64_t> pbb((size_t)NB, 0);
     if (B.reuse)
         for (int g = 0; g < B.G; ++g)
             for (int64_t b = B.g_bin[(size_t)g]; b < B.g_bin[(size_t)g + 1]; ++b) pbb[(size_t)b] = B.g_prod[(size_t)g];
-    void *q;
     // val1 / cs1 / dst1 over the Mul positions [0, E1) with the Mul's
     // unclamped-batch slack (kBinMulSlack), zeroed past the entries (Mul
     // order: the entries fill [0, nnz) unpadded, the rest is slack).  With
@@ -418,24 +373,20 @@ int bin_fill_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, c
     // first, and every destination group points at the trash line (dst_fill)
     // until a segment claims it -- as the host fill leaves them.
     const int64_t Ez = LL > 0 ? 0 : B.mo ? p->nnz : E;
-    SPMV_RETURN_IF(p->arena.alloc(&q, sizeof(double) * (size_t)(E1 + kBinMulSlack)));
-    B.val1 = (double *)q;
+    SPMV_RETURN_IF(plan_alloc(p, &B.val1, E1 + kBinMulSlack));
     SPMV_HIP_TRY(hipMemsetAsync(B.val1 + Ez, 0, sizeof(double) * (size_t)(E1 - Ez + kBinMulSlack), st));
-    SPMV_RETURN_IF(p->arena.alloc(&q, sizeof(uint16_t) * (size_t)(E1 + kBinMulSlack)));
-    B.cs1 = (uint16_t *)q;
+    SPMV_RETURN_IF(plan_alloc(p, &B.cs1, E1 + kBinMulSlack));
     SPMV_HIP_TRY(hipMemsetAsync(B.cs1 + Ez, 0, sizeof(uint16_t) * (size_t)(E1 - Ez + kBinMulSlack), st));
-    SPMV_RETURN_IF(p->arena.alloc(&q, sizeof(uint16_t) * (size_t)std::max<int64_t>(ES, 1)));
-    B.slot2 = (uint16_t *)q;
+    SPMV_RETURN_IF(plan_alloc(p, &B.slot2, ES));
     if (!B.mo) {  // Mul-ordered products need no destinations
         const int64_t nd = (E1 + kBinMulSlack) >> B.pad_log;
-        SPMV_RETURN_IF(p->arena.alloc(&q, sizeof(int32_t) * (size_t)std::max<int64_t>(nd, 1)));
-        B.dst1 = (int32_t *)q;
+        SPMV_RETURN_IF(plan_alloc(p, &B.dst1, nd));
         if (LL > 0)
-            hipLaunchKernelGGL(fill_i32_kernel, dim3(grid_of(nd)), dim3(256), 0, st, B.dst1, nd, dst_fill);
+            hipLaunchKernelGGL(fill_i32_kernel, dim3(grid_for(nd)), dim3(256), 0, st, B.dst1, nd, dst_fill);
         else
             SPMV_HIP_TRY(hipMemsetAsync(B.dst1 + (E >> B.pad_log), 0, sizeof(int32_t) * (size_t)(kBinMulSlack >> B.pad_log), st));
     }
-    Scratch sc{st, {}};
+    DevScratch sc(st);
     int32_t *d_row0, *d_cnt;
     int64_t *d_bstart, *d_off1, *d_off2, *d_cbase, *d_pbb, *d_run, *d_srun;
     // cbase: entries of the segments before each one in the Sum order
@@ -449,57 +400,57 @@ int bin_fill_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, c
             for (int64_t b = 0; b < NB; ++b)
                 for (int64_t t = k * SB; t < std::min(S, (k + 1) * SB); ++t) {
                     cbase[(size_t)(b * S + t)] = n_seg;
-                    n_seg += cnt[(size_t)(b * S + t)];
+                    n_seg += L.cnt[(size_t)(b * S + t)];
                 }
     }
-    SPMV_RETURN_IF(sc.upload(&d_row0, row0));
+    SPMV_RETURN_IF(sc.upload(&d_row0, L.row0));
     SPMV_RETURN_IF(sc.upload(&d_bstart, bstart));
-    SPMV_RETURN_IF(sc.upload(&d_cnt, cnt));
-    SPMV_RETURN_IF(sc.upload(&d_off1, off1));
-    SPMV_RETURN_IF(sc.upload(&d_off2, off2));
+    SPMV_RETURN_IF(sc.upload(&d_cnt, L.cnt));
+    SPMV_RETURN_IF(sc.upload(&d_off1, L.off1));
+    SPMV_RETURN_IF(sc.upload(&d_off2, L.off2));
     SPMV_RETURN_IF(sc.upload(&d_cbase, cbase));
-    SPMV_RETURN_IF(sc.upload(&d_run, run_off));
-    SPMV_RETURN_IF(sc.upload(&d_srun, srun_off));
+    SPMV_RETURN_IF(sc.upload(&d_run, L.run_off));
+    SPMV_RETURN_IF(sc.upload(&d_srun, L.srun_off));
     // every slot starts as the dummy slot (segment padding and the padding of
     // each slot run to whole Sum batches)
-    hipLaunchKernelGGL(fill_u16_kernel, dim3(grid_of(ES)), dim3(256), 0, st, B.slot2, ES, (uint16_t)B.max_rows);
+    hipLaunchKernelGGL(fill_u16_kernel, dim3(grid_for(ES)), dim3(256), 0, st, B.slot2, ES, (uint16_t)B.max_rows);
     SPMV_RETURN_IF(sc.upload(&d_pbb, pbb));
-    const SortPlaceArgs A{d_rp, d_col, d_val, NB, S, d_row0, d_bstart, d_off1, d_off2, d_cbase, d_pbb, d_run, d_srun,
-                          E, LL, n_seg};
+    const SortPlaceArgs SP{A.d_rp, A.d_col, A.d_val, NB, S, d_row0, d_bstart, d_off1, d_off2, d_cbase, d_pbb, d_run,
+                           d_srun, E, LL, n_seg};
     if (E < ((int64_t)1 << 32) - 1 && p->nnz < ((int64_t)1 << 32))
-        SPMV_RETURN_IF((bin_sort_place<uint32_t, uint32_t>(p, sc, A)));
+        SPMV_RETURN_IF((bin_sort_place<uint32_t, uint32_t>(p, sc, SP)));
     else
-        SPMV_RETURN_IF((bin_sort_place<uint64_t, uint64_t>(p, sc, A)));
+        SPMV_RETURN_IF((bin_sort_place<uint64_t, uint64_t>(p, sc, SP)));
     if (!B.mo)  // (Mul order: the Mul's segments are not padded)
-        hipLaunchKernelGGL(bin_pad_kernel, dim3(grid_of(NB * S)), dim3(256), 0, st, d_cnt, NB * S, d_off1, B.pad_log,
+        hipLaunchKernelGGL(bin_pad_kernel, dim3(grid_for(NB * S)), dim3(256), 0, st, d_cnt, NB * S, d_off1, B.pad_log,
                            B.val1, B.cs1);
-    return finish(st, "fill");
+    return build_sync(st, "BIN device build (fill)");
 }
 
-int bin_long_runs_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, const std::vector<int32_t> &lrows,
+int bin_long_runs_device(spmv_plan_s *p, const DevCsr &A, const std::vector<int32_t> &lrows,
                          std::vector<int64_t> &roff, std::vector<int32_t> &rstrip, std::vector<int64_t> &rbeg) {
     const hipStream_t st = p->stream;
     const int64_t nl = (int64_t)lrows.size();
-    const unsigned grid = (unsigned)std::max<int64_t>(1, (nl + 3) / 4);
-    Scratch sc{st, {}};
+    const unsigned grid = waves_grid(nl);
+    DevScratch sc(st);
     int32_t *d_lrows, *d_n, *d_strip;
     int64_t *d_roff, *d_beg;
     SPMV_RETURN_IF(sc.upload(&d_lrows, lrows));
-    SPMV_RETURN_IF(sc.alloc(&d_n, (size_t)nl));
-    hipLaunchKernelGGL(bin_long_runs_kernel, dim3(grid), dim3(256), 0, st, nl, d_lrows, d_rp, d_col,
+    SPMV_RETURN_IF(sc.alloc(&d_n, (size_t)nl, "BIN long-row run counts"));
+    hipLaunchKernelGGL(bin_long_runs_kernel, dim3(grid), dim3(256), 0, st, nl, d_lrows, A.d_rp, A.d_col,
                        (int32_t)p->bin.strip, (const int64_t *)nullptr, d_n, (int32_t *)nullptr, (int64_t *)nullptr);
-    SPMV_RETURN_IF(finish(st, "long-row runs"));
+    SPMV_RETURN_IF(build_sync(st, "BIN device build (long-row runs)"));
     std::vector<int32_t> n((size_t)nl);
     SPMV_HIP_TRY(hipMemcpy(n.data(), d_n, sizeof(int32_t) * (size_t)nl, hipMemcpyDeviceToHost));
     roff.assign((size_t)nl + 1, 0);
     for (int64_t i = 0; i < nl; ++i) roff[(size_t)i + 1] = roff[(size_t)i] + n[(size_t)i];
     const int64_t R = roff[(size_t)nl];
     SPMV_RETURN_IF(sc.upload(&d_roff, roff));
-    SPMV_RETURN_IF(sc.alloc(&d_strip, (size_t)R));
-    SPMV_RETURN_IF(sc.alloc(&d_beg, (size_t)R));
-    hipLaunchKernelGGL(bin_long_runs_kernel, dim3(grid), dim3(256), 0, st, nl, d_lrows, d_rp, d_col,
+    SPMV_RETURN_IF(sc.alloc(&d_strip, (size_t)R, "BIN long-row run strips"));
+    SPMV_RETURN_IF(sc.alloc(&d_beg, (size_t)R, "BIN long-row run starts"));
+    hipLaunchKernelGGL(bin_long_runs_kernel, dim3(grid), dim3(256), 0, st, nl, d_lrows, A.d_rp, A.d_col,
                        (int32_t)p->bin.strip, (const int64_t *)d_roff, d_n, d_strip, d_beg);
-    SPMV_RETURN_IF(finish(st, "long-row runs"));
+    SPMV_RETURN_IF(build_sync(st, "BIN device build (long-row runs)"));
     rstrip.resize((size_t)R);
     rbeg.resize((size_t)R);
     SPMV_HIP_TRY(hipMemcpy(rstrip.data(), d_strip, sizeof(int32_t) * (size_t)R, hipMemcpyDeviceToHost));
@@ -507,19 +458,12 @@ int bin_long_runs_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_c
     return SPMV_SUCCESS;
 }
 
-int bin_long_fill_device(spmv_plan_s *p, const int32_t *d_col, const double *d_val, const BinLongRuns &LR,
-                         const std::vector<int64_t> &lb_off, const std::vector<int64_t> &lpad,
-                         const std::vector<int64_t> &lstart, const std::vector<int64_t> &lcode_off,
-                         const std::vector<int64_t> &run_off, const std::vector<int64_t> &srun_off, int64_t lrun0,
-                         int64_t trash) {
+int bin_long_fill_device(spmv_plan_s *p, const DevCsr &A, const BinLayout &L, const BinLongRuns &LR, int64_t lrun0) {
     BinDev &B = p->bin;
     const hipStream_t st = p->stream;
-    const int64_t S = (int64_t)lpad.size(), R = (int64_t)LR.j0.size();
-    void *q;
-    const int64_t ncode = lcode_off.back() + lpad.back();
-    SPMV_RETURN_IF(p->arena.alloc(&q, sizeof(int32_t) * (size_t)std::max<int64_t>(ncode, 1)));
-    B.lcode = (int32_t *)q;
-    Scratch sc{st, {}};
+    const int64_t S = L.S, R = (int64_t)LR.j0.size();
+    SPMV_RETURN_IF(plan_alloc(p, &B.lcode, L.lcode_off.back() + L.lpad.back()));
+    DevScratch sc(st);
     int64_t *d_j0, *d_q0, *d_fpos, *d_lb, *d_lpad, *d_lstart, *d_lco, *d_run, *d_srun;
     int32_t *d_len, *d_strip, *d_slot, *d_bin;
     SPMV_RETURN_IF(sc.upload(&d_j0, LR.j0));
@@ -529,26 +473,24 @@ int bin_long_fill_device(spmv_plan_s *p, const int32_t *d_col, const double *d_v
     SPMV_RETURN_IF(sc.upload(&d_strip, LR.strip));
     SPMV_RETURN_IF(sc.upload(&d_slot, LR.slot));
     SPMV_RETURN_IF(sc.upload(&d_bin, LR.bin));
-    SPMV_RETURN_IF(sc.upload(&d_lb, lb_off));
-    SPMV_RETURN_IF(sc.upload(&d_lpad, lpad));
-    SPMV_RETURN_IF(sc.upload(&d_lstart, lstart));
-    SPMV_RETURN_IF(sc.upload(&d_lco, lcode_off));
-    SPMV_RETURN_IF(sc.upload(&d_run, run_off));
-    SPMV_RETURN_IF(sc.upload(&d_srun, srun_off));
+    SPMV_RETURN_IF(sc.upload(&d_lb, L.lb_off));
+    SPMV_RETURN_IF(sc.upload(&d_lpad, L.lpad));
+    SPMV_RETURN_IF(sc.upload(&d_lstart, L.lstart));
+    SPMV_RETURN_IF(sc.upload(&d_lco, L.lcode_off));
+    SPMV_RETURN_IF(sc.upload(&d_run, L.run_off));
+    SPMV_RETURN_IF(sc.upload(&d_srun, L.srun_off));
     if (R > 0)
-        hipLaunchKernelGGL(bin_long_fill_kernel, dim3((unsigned)std::max<int64_t>(1, (R + 3) / 4)), dim3(256), 0, st, R,
-                           d_j0, d_len, d_strip, d_slot, d_bin, d_q0, d_fpos, d_col, d_val, (int32_t)B.strip, d_lstart,
-                           d_lco, d_run, d_srun, lrun0, B.sum_u, B.val1, B.cs1, B.lcode, B.slot2);
-    hipLaunchKernelGGL(bin_long_pad_kernel, dim3(grid_of(S)), dim3(256), 0, st, S, d_lb, d_lpad, d_lco, (int32_t)trash,
-                       B.lcode);
-    return finish(st, "long rows");
+        hipLaunchKernelGGL(bin_long_fill_kernel, dim3(waves_grid(R)), dim3(256), 0, st, R, d_j0, d_len, d_strip, d_slot,
+                           d_bin, d_q0, d_fpos, A.d_col, A.d_val, (int32_t)B.strip, d_lstart, d_lco, d_run, d_srun,
+                           lrun0, B.sum_u, B.val1, B.cs1, B.lcode, B.slot2);
+    hipLaunchKernelGGL(bin_long_pad_kernel, dim3(grid_for(S)), dim3(256), 0, st, S, d_lb, d_lpad, d_lco,
+                       (int32_t)L.TRASH, B.lcode);
+    return build_sync(st, "BIN device build (long rows)");
 }
 
-int bin_sort_rows_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, const double *d_val,
-                         int32_t *col2, double *val2) {
-    Scratch sc{p->stream, {}};
-    if (p->nnz < ((int64_t)1 << 32)) return bin_sort_rows_t<uint32_t>(p, sc, d_rp, d_col, d_val, col2, val2);
-    return bin_sort_rows_t<uint64_t>(p, sc, d_rp, d_col, d_val, col2, val2);
+int bin_sort_rows_device(spmv_plan_s *p, const DevCsr &A, int32_t *col2, double *val2) {
+    if (p->nnz < ((int64_t)1 << 32)) return bin_sort_rows_t<uint32_t>(p, A, col2, val2);
+    return bin_sort_rows_t<uint64_t>(p, A, col2, val2);
 }
 
 }  // namespace spmv

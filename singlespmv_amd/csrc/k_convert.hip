@@ -14,12 +14,10 @@
 #include <cstdlib>
 #include <vector>
 
+#include "build_util.hpp"
 #include "device.hpp"
-#include "internal.hpp"
 
 namespace spmv {
-
-int csr_x_windows_device(spmv_plan_s *p, const int64_t *d_rp);
 
 namespace {
 
@@ -56,17 +54,16 @@ __global__ __launch_bounds__(kScanBlock) void scan_block_apply(const int64_t *__
     if (i < n) out[i] = offs[blockIdx.x] + s[threadIdx.x] - v;  // exclusive
 }
 
-int exclusive_scan(spmv_plan_s *p, const int64_t *in, int64_t *out, int64_t n, hipStream_t st,
-                   std::vector<void *> &tmp) {
+// (the block sums and offsets of every level live in sc until the caller is done)
+int exclusive_scan(const int64_t *in, int64_t *out, int64_t n, DevScratch &sc) {
     if (n == 0) return SPMV_SUCCESS;
+    const hipStream_t st = sc.st;
     const int64_t nb = (n + kScanBlock - 1) / kScanBlock;
     int64_t *sums, *offs;
-    SPMV_RETURN_IF(scratch_malloc(&sums, sizeof(int64_t) * nb, "sums"));
-    tmp.push_back(sums);
-    SPMV_RETURN_IF(scratch_malloc(&offs, sizeof(int64_t) * nb, "offs"));
-    tmp.push_back(offs);
+    SPMV_RETURN_IF(sc.alloc(&sums, (size_t)nb, "sums"));
+    SPMV_RETURN_IF(sc.alloc(&offs, (size_t)nb, "offs"));
     hipLaunchKernelGGL(scan_block_sums, dim3((unsigned)nb), dim3(kScanBlock), 0, st, in, n, sums);
-    if (nb > 1) SPMV_RETURN_IF(exclusive_scan(p, sums, offs, nb, st, tmp));
+    if (nb > 1) SPMV_RETURN_IF(exclusive_scan(sums, offs, nb, sc));
     else SPMV_HIP_TRY(hipMemsetAsync(offs, 0, sizeof(int64_t), st));
     hipLaunchKernelGGL(scan_block_apply, dim3((unsigned)nb), dim3(kScanBlock), 0, st, in, n, offs, out);
     SPMV_HIP_TRY(hipGetLastError());
@@ -205,13 +202,7 @@ __global__ void scale_kernel(double *__restrict__ y, int64_t n, double alpha) {
         y[i] = __dmul_rn(alpha, y[i]);
 }
 
-inline unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 65536)); }
-
 }  // namespace
-
-int exclusive_scan_i64(const int64_t *in, int64_t *out, int64_t n, hipStream_t st, std::vector<void *> &tmp) {
-    return exclusive_scan(nullptr, in, out, n, st, tmp);
-}
 
 int widen_row_ptr_device(const int32_t *d_rp32, int64_t m, int64_t **d_rp64) {
     *d_rp64 = nullptr;
@@ -255,46 +246,6 @@ int validate_csr_device(const int64_t *d_rp, int64_t m, const int32_t *d_col, in
     return SPMV_SUCCESS;
 }
 
-// Device-input plan builders.  d_rp/d_col/d_val are device pointers on the
-// plan's device; they are only read.
-int build_csr_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, const double *d_val,
-                     const spmv_options_t &o, double mean_row) {
-    CsrDev &c = p->csr;
-    const hipStream_t st = p->stream;
-    c.rp64 = p->nnz >= (int64_t)INT32_MAX - 64 || o.csr_row_ptr64 != 0 || probe_env("SPMV_CSR_FORCE_RP64");
-    void *q;
-    SPMV_RETURN_IF(p->arena.alloc(&q, (c.rp64 ? 8 : 4) * (size_t)(p->m + 1)));
-    c.row_ptr = q;
-    if (c.rp64) SPMV_HIP_TRY(hipMemcpyAsync(q, d_rp, 8 * (size_t)(p->m + 1), hipMemcpyDeviceToDevice, st));
-    else hipLaunchKernelGGL(rp_to_i32, dim3(grid_for(p->m + 1)), dim3(256), 0, st, d_rp, p->m + 1, (int32_t *)q);
-    SPMV_RETURN_IF(p->arena.alloc(&q, sizeof(int32_t) * (size_t)(p->nnz + kPad)));
-    c.col = (int32_t *)q;
-    if (p->nnz) SPMV_HIP_TRY(hipMemcpyAsync(c.col, d_col, 4 * (size_t)p->nnz, hipMemcpyDeviceToDevice, st));
-    SPMV_HIP_TRY(hipMemsetAsync(c.col + p->nnz, 0, 4 * kPad, st));
-    SPMV_HIP_TRY(hipStreamSynchronize(st));
-    (void)mean_row;
-    // lanes per row / length bins from the row pointers (m+1 values to the host)
-    std::vector<int64_t> hrp((size_t)p->m + 1);
-    SPMV_HIP_TRY(hipMemcpy(hrp.data(), d_rp, 8 * (size_t)(p->m + 1), hipMemcpyDeviceToHost));
-    SPMV_RETURN_IF(csr_plan_lanes(p, hrp.data(), p->m, o));
-    c.val_halves = csr_val_halves_wanted(c);
-    const int64_t vtotal = c.val_halves ? (p->nnz + 255) / 256 * 256 : p->nnz;
-    SPMV_RETURN_IF(p->arena.alloc(&q, sizeof(double) * (size_t)(vtotal + kPad)));
-    c.val = (double *)q;
-    if (c.val_halves) {
-        hipLaunchKernelGGL(csr_val_halves_kernel, dim3(grid_for(vtotal)), dim3(256), 0, st, d_val, p->nnz, vtotal,
-                           c.val);
-    } else if (p->nnz) {
-        SPMV_HIP_TRY(hipMemcpyAsync(c.val, d_val, 8 * (size_t)p->nnz, hipMemcpyDeviceToDevice, st));
-    }
-    SPMV_HIP_TRY(hipMemsetAsync(c.val + vtotal, 0, 8 * kPad, st));
-    SPMV_HIP_TRY(hipGetLastError());
-    SPMV_HIP_TRY(hipStreamSynchronize(st));
-    if (c.lanes > 0) SPMV_RETURN_IF(csr_x_windows_device(p, d_rp));
-    csr_finish_info(p);
-    return SPMV_SUCCESS;
-}
-
 // csr_x_windows on the device (formats.cpp): the column range [lo, hi] of
 // each kCsrWinGroup-row granule's entries (hi = -1: none), one workgroup each
 __global__ __launch_bounds__(256) void csr_window_kernel(const int64_t *__restrict__ rp, int64_t m,
@@ -327,96 +278,103 @@ __global__ __launch_bounds__(256) void csr_window_kernel(const int64_t *__restri
     }
 }
 
-int csr_x_windows_device(spmv_plan_s *p, const int64_t *d_rp) {
+static int csr_x_windows_device(spmv_plan_s *p, const int64_t *d_rp) {
     const int64_t ng = (p->m + kCsrWinGroup - 1) / kCsrWinGroup;
     if (ng == 0) return SPMV_SUCCESS;
+    DevScratch sc(p->stream);
     int32_t *d = nullptr;
-    SPMV_RETURN_IF(scratch_malloc(&d, 2 * sizeof(int32_t) * (size_t)ng, "d"));
+    SPMV_RETURN_IF(sc.alloc(&d, 2 * (size_t)ng, "d"));
     hipLaunchKernelGGL(csr_window_kernel, dim3((unsigned)ng), dim3(256), 0, p->stream, d_rp, p->m, p->csr.col, d,
                        d + ng);
     std::vector<int32_t> lo((size_t)ng), hi((size_t)ng);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(lo.data(), d, sizeof(int32_t) * (size_t)ng, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(hi.data(), d + ng, sizeof(int32_t) * (size_t)ng, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    SPMV_HIP_TRY(e);
+    SPMV_HIP_TRY(hipGetLastError());
+    SPMV_HIP_TRY(hipMemcpy(lo.data(), d, sizeof(int32_t) * (size_t)ng, hipMemcpyDeviceToHost));
+    SPMV_HIP_TRY(hipMemcpy(hi.data(), d + ng, sizeof(int32_t) * (size_t)ng, hipMemcpyDeviceToHost));
     return csr_windows_finish(p, lo, hi);
 }
 
-int build_ss_device(spmv_plan_s *p, const int64_t *d_rp, const int32_t *d_col, const double *d_val,
-                    const spmv_options_t &o, double mean_row) {
+// Device-input plan builders.  A's arrays are device pointers on the plan's
+// device; they are only read.
+int build_csr_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o) {
+    CsrDev &c = p->csr;
+    const hipStream_t st = p->stream;
+    c.rp64 = p->nnz >= (int64_t)INT32_MAX - 64 || o.csr_row_ptr64 != 0 || probe_env("SPMV_CSR_FORCE_RP64");
+    SPMV_RETURN_IF(p->arena.alloc(&c.row_ptr, (c.rp64 ? 8 : 4) * (size_t)(p->m + 1)));
+    if (c.rp64) SPMV_HIP_TRY(hipMemcpyAsync(c.row_ptr, A.d_rp, 8 * (size_t)(p->m + 1), hipMemcpyDeviceToDevice, st));
+    else
+        hipLaunchKernelGGL(rp_to_i32, dim3(grid_for(p->m + 1)), dim3(256), 0, st, A.d_rp, p->m + 1,
+                           (int32_t *)c.row_ptr);
+    SPMV_RETURN_IF(plan_alloc(p, &c.col, p->nnz + kPad));
+    if (p->nnz) SPMV_HIP_TRY(hipMemcpyAsync(c.col, A.d_col, 4 * (size_t)p->nnz, hipMemcpyDeviceToDevice, st));
+    SPMV_HIP_TRY(hipMemsetAsync(c.col + p->nnz, 0, 4 * kPad, st));
+    SPMV_HIP_TRY(hipStreamSynchronize(st));
+    // lanes per row / length bins from the host copy of the row pointers
+    SPMV_RETURN_IF(csr_plan_lanes(p, A.h_rp, p->m, o));
+    c.val_halves = csr_val_halves_wanted(c);
+    const int64_t vtotal = c.val_halves ? (p->nnz + 255) / 256 * 256 : p->nnz;
+    SPMV_RETURN_IF(plan_alloc(p, &c.val, vtotal + kPad));
+    if (c.val_halves) {
+        hipLaunchKernelGGL(csr_val_halves_kernel, dim3(grid_for(vtotal)), dim3(256), 0, st, A.d_val, p->nnz, vtotal,
+                           c.val);
+    } else if (p->nnz) {
+        SPMV_HIP_TRY(hipMemcpyAsync(c.val, A.d_val, 8 * (size_t)p->nnz, hipMemcpyDeviceToDevice, st));
+    }
+    SPMV_HIP_TRY(hipMemsetAsync(c.val + vtotal, 0, 8 * kPad, st));
+    SPMV_HIP_TRY(hipGetLastError());
+    SPMV_HIP_TRY(hipStreamSynchronize(st));
+    if (c.lanes > 0) SPMV_RETURN_IF(csr_x_windows_device(p, A.d_rp));
+    csr_finish_info(p);
+    return SPMV_SUCCESS;
+}
+
+int build_ss_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o) {
     SsDev &s = p->ss;
     const hipStream_t st = p->stream;
-    s.sigma = o.ss_sigma > 0 ? o.ss_sigma : auto_ss_sigma(mean_row);
+    const int64_t m = p->m, nnz = p->nnz;
+    s.sigma = o.ss_sigma > 0 ? o.ss_sigma : auto_ss_sigma(m ? (double)nnz / (double)m : 0.0);
     if (!ss_sigma_ok(s.sigma)) {
         set_error("ss_sigma must be one of 4,8,12,16,20,24,32,48,64");
         return SPMV_ERROR_INVALID_VALUE;
     }
     ss_probe_options(s);
     const int W = ss_flag_words(s.sigma);
-    const int64_t m = p->m, nnz = p->nnz, T = 64 * (int64_t)s.sigma;
+    const int64_t T = 64 * (int64_t)s.sigma;
     s.n_tiles = (nnz + T - 1) / T;
-    // scratch freed on every exit path (after the stream drains)
-    struct Scratch {
-        hipStream_t st;
-        std::vector<void *> v;
-        ~Scratch() {
-            (void)hipStreamSynchronize(st);
-            for (void *t : v) (void)hipFree(t);
-        }
-    } scratch{st, {}};
-    std::vector<void *> &tmp = scratch.v;
+    const int64_t tiles1 = std::max<int64_t>(s.n_tiles, 1), total = s.n_tiles * T;
+    DevScratch sc(st);
     // non-empty ordinals
     int64_t *flg = nullptr, *nzord = nullptr;
-    SPMV_RETURN_IF(scratch_malloc(&flg, 8 * (size_t)std::max<int64_t>(m + 1, 1), "flg"));
-    tmp.push_back(flg);
-    SPMV_RETURN_IF(scratch_malloc(&nzord, 8 * (size_t)std::max<int64_t>(m + 1, 1), "nzord"));
-    tmp.push_back(nzord);
-    hipLaunchKernelGGL(nonempty_flags, dim3(grid_for(m)), dim3(256), 0, st, d_rp, m, flg);
+    SPMV_RETURN_IF(sc.alloc(&flg, (size_t)m + 1, "flg"));
+    SPMV_RETURN_IF(sc.alloc(&nzord, (size_t)m + 1, "nzord"));
+    hipLaunchKernelGGL(nonempty_flags, dim3(grid_for(m)), dim3(256), 0, st, A.d_rp, m, flg);
     SPMV_HIP_TRY(hipMemsetAsync(flg + m, 0, 8, st));
-    SPMV_RETURN_IF(exclusive_scan(p, flg, nzord, m + 1, st, tmp));
+    SPMV_RETURN_IF(exclusive_scan(flg, nzord, m + 1, sc));
     SPMV_HIP_TRY(hipMemcpyAsync(&s.n_nonempty, nzord + m, 8, hipMemcpyDeviceToHost, st));
     SPMV_HIP_TRY(hipStreamSynchronize(st));
     s.n_empty = m - s.n_nonempty;
-    void *q;
     if (s.n_empty > 0) {
-        SPMV_RETURN_IF(p->arena.alloc(&q, 4 * (size_t)std::max<int64_t>(s.n_nonempty, 1)));
-        s.nzrow = (int32_t *)q;
-        SPMV_RETURN_IF(p->arena.alloc(&q, 4 * (size_t)s.n_empty));
-        s.empty_rows = (int32_t *)q;
-        hipLaunchKernelGGL(compact_rows, dim3(grid_for(m)), dim3(256), 0, st, d_rp, nzord, m, s.nzrow, s.empty_rows);
+        SPMV_RETURN_IF(plan_alloc(p, &s.nzrow, s.n_nonempty));
+        SPMV_RETURN_IF(plan_alloc(p, &s.empty_rows, s.n_empty));
+        hipLaunchKernelGGL(compact_rows, dim3(grid_for(m)), dim3(256), 0, st, A.d_rp, nzord, m, s.nzrow, s.empty_rows);
     }
-    const int64_t total = s.n_tiles * T;
-    SPMV_RETURN_IF(p->arena.alloc(&q, 4 * (size_t)std::max<int64_t>(s.n_tiles * 64 * W, 1)));
-    s.flags = (uint32_t *)q;
+    SPMV_RETURN_IF(plan_alloc(p, &s.flags, s.n_tiles * 64 * W));
     SPMV_HIP_TRY(hipMemsetAsync(s.flags, 0, 4 * (size_t)std::max<int64_t>(s.n_tiles * 64 * W, 1), st));
-    hipLaunchKernelGGL(start_flags, dim3(grid_for(m + 1)), dim3(256), 0, st, d_rp, m, nnz, s.sigma, s.flags);
-    SPMV_RETURN_IF(p->arena.alloc(&q, 4 * (size_t)std::max<int64_t>(s.n_tiles, 1)));
-    s.tile_ord = (int32_t *)q;
-    hipLaunchKernelGGL(tile_ordinals, dim3(grid_for(s.n_tiles)), dim3(256), 0, st, d_rp, m,
-                       nzord, s.n_nonempty, s.sigma, s.n_tiles, s.tile_ord);
-    SPMV_RETURN_IF(p->arena.alloc(&q, 4 * (size_t)std::max<int64_t>(total, 1)));
-    s.col = (int32_t *)q;
-    SPMV_RETURN_IF(p->arena.alloc(&q, 8 * (size_t)std::max<int64_t>(total, 1)));
-    s.val = (double *)q;
-    hipLaunchKernelGGL(tile_transpose, dim3(grid_for(total)), dim3(256), 0, st, d_col, d_val, nnz, s.sigma, total,
+    hipLaunchKernelGGL(start_flags, dim3(grid_for(m + 1)), dim3(256), 0, st, A.d_rp, m, nnz, s.sigma, s.flags);
+    SPMV_RETURN_IF(plan_alloc(p, &s.tile_ord, s.n_tiles));
+    hipLaunchKernelGGL(tile_ordinals, dim3(grid_for(s.n_tiles)), dim3(256), 0, st, A.d_rp, m, nzord, s.n_nonempty,
+                       s.sigma, s.n_tiles, s.tile_ord);
+    SPMV_RETURN_IF(plan_alloc(p, &s.col, total));
+    SPMV_RETURN_IF(plan_alloc(p, &s.val, total));
+    hipLaunchKernelGGL(tile_transpose, dim3(grid_for(total)), dim3(256), 0, st, A.d_col, A.d_val, nnz, s.sigma, total,
                        s.col, s.val);
-    SPMV_RETURN_IF(p->arena.alloc(&q, 8 * (size_t)std::max<int64_t>(s.n_tiles, 1)));
-    s.win = (int32_t *)q;
+    SPMV_RETURN_IF(plan_alloc(p, &s.win, 2 * tiles1));
     if (s.n_tiles > 0)
-        hipLaunchKernelGGL(tile_windows, dim3((unsigned)((s.n_tiles + 3) / 4)), dim3(256), 0, st, d_col, nnz, s.sigma,
+        hipLaunchKernelGGL(tile_windows, dim3(waves_grid(s.n_tiles)), dim3(256), 0, st, A.d_col, nnz, s.sigma,
                            s.n_tiles, s.win);
-    SPMV_RETURN_IF(p->arena.alloc(&q, 16 * (size_t)std::max<int64_t>(s.n_tiles, 1)));
-    s.ht = (double *)q;
-    SPMV_RETURN_IF(p->arena.alloc(&q, 4 * (size_t)std::max<int64_t>(s.n_tiles, 1)));
-    s.tail_ord = (int32_t *)q;
+    SPMV_RETURN_IF(plan_alloc(p, &s.ht, 2 * tiles1));
+    SPMV_RETURN_IF(plan_alloc(p, &s.tail_ord, s.n_tiles));
     SPMV_RETURN_IF(ss_plan_tail_ord(p));
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        set_error(std::string("device SS conversion: ") + hipGetErrorString(e));
-        return SPMV_ERROR_HIP;
-    }
+    SPMV_RETURN_IF(build_sync(st, "device SS conversion"));
     ss_finish_info(p);
     return SPMV_SUCCESS;
 }

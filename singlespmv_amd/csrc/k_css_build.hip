@@ -11,8 +11,8 @@
 // 32-bit entry limit.
 #include <hipcub/hipcub.hpp>
 
+#include "build_util.hpp"
 #include "device.hpp"
-#include "internal.hpp"
 
 namespace spmv {
 
@@ -67,43 +67,6 @@ __global__ void css_fill_u16(uint16_t *__restrict__ a, int64_t n, uint16_t v) {
         a[i] = v;
 }
 
-unsigned waves_grid(int64_t waves) { return (unsigned)std::max<int64_t>(1, (waves + 3) / 4); }
-
-struct Scratch {
-    hipStream_t st;
-    std::vector<void *> v;
-    ~Scratch() {
-        (void)hipStreamSynchronize(st);
-        for (void *t : v) (void)hipFree(t);
-    }
-    template <typename T>
-    int alloc(T **q, size_t count) {
-        void *t = nullptr;
-        if (hipMalloc(&t, sizeof(T) * std::max<size_t>(count, 1)) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("device CSS build: out of device memory for scratch");
-            return SPMV_ERROR_OUT_OF_MEMORY;
-        }
-        v.push_back(t);
-        *q = (T *)t;
-        return SPMV_SUCCESS;
-    }
-    template <typename T>
-    int upload(T **q, const std::vector<T> &h) {
-        SPMV_RETURN_IF(alloc(q, h.size()));
-        if (!h.empty()) SPMV_HIP_TRY(hipMemcpyAsync(*q, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, st));
-        return SPMV_SUCCESS;
-    }
-};
-
-template <typename T>
-int plan_alloc(spmv_plan_s *p, T **dst, int64_t count) {
-    void *q = nullptr;
-    SPMV_RETURN_IF(p->arena.alloc(&q, sizeof(T) * (size_t)std::max<int64_t>(count, 1)));
-    *dst = (T *)q;
-    return SPMV_SUCCESS;
-}
-
 }  // namespace
 
 int build_css_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o) {
@@ -141,10 +104,10 @@ int build_css_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o) {
     SPMV_HIP_TRY(hipMemsetAsync(c.val, 0, sizeof(double) * (size_t)(total + 256), st));
     SPMV_HIP_TRY(hipMemsetAsync(c.row + total, 0, sizeof(uint16_t) * 256, st));
     if (total > 0)
-        hipLaunchKernelGGL(css_fill_u16, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 65536)), dim3(256), 0,
+        hipLaunchKernelGGL(css_fill_u16, dim3(grid_for(total)), dim3(256), 0,
                            st, c.row, total, (uint16_t)kCssMaxRows);
     if (A.nnz > 0) {
-        Scratch sc{st, {}};
+        DevScratch sc(st);
         int64_t *d_poff, *d_pb, *d_pe, *d_woff, *d_eoff;
         int32_t *d_ps;
         uint64_t *k_in, *k_out, *v_in, *v_out;
@@ -154,10 +117,10 @@ int build_css_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o) {
         SPMV_RETURN_IF(sc.upload(&d_ps, ps));
         SPMV_RETURN_IF(sc.upload(&d_eoff, eoff));
         SPMV_RETURN_IF(sc.upload(&d_woff, CL.woff));
-        SPMV_RETURN_IF(sc.alloc(&k_in, (size_t)A.nnz));
-        SPMV_RETURN_IF(sc.alloc(&k_out, (size_t)A.nnz));
-        SPMV_RETURN_IF(sc.alloc(&v_in, (size_t)A.nnz));
-        SPMV_RETURN_IF(sc.alloc(&v_out, (size_t)A.nnz));
+        SPMV_RETURN_IF(sc.alloc(&k_in, (size_t)A.nnz, "CSS sort keys"));
+        SPMV_RETURN_IF(sc.alloc(&k_out, (size_t)A.nnz, "CSS sort keys"));
+        SPMV_RETURN_IF(sc.alloc(&v_in, (size_t)A.nnz, "CSS sort values"));
+        SPMV_RETURN_IF(sc.alloc(&v_out, (size_t)A.nnz, "CSS sort values"));
         // key bits: the column's, then the list's above them
         int cbits = 1, lbits = 1;
         while (cbits < 31 && ((int64_t)1 << cbits) < A.n) ++cbits;
@@ -167,19 +130,13 @@ int build_css_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o) {
         hipcub::DoubleBuffer<uint64_t> dk(k_in, k_out), dv(v_in, v_out);
         size_t tb = 0;
         SPMV_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dk, dv, A.nnz, 0, cbits + lbits, st));
-        void *tmp = nullptr;
-        SPMV_RETURN_IF(sc.alloc((char **)&tmp, tb));
+        char *tmp = nullptr;
+        SPMV_RETURN_IF(sc.alloc(&tmp, tb, "CSS sort workspace"));
         SPMV_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, dk, dv, A.nnz, 0, cbits + lbits, st));
         hipLaunchKernelGGL(css_scatter_kernel, dim3(waves_grid(nl)), dim3(256), 0, st, nl, d_eoff, d_woff,
                            c.chunk_stride, (const uint64_t *)dk.Current(), cbits, (const uint64_t *)dv.Current(), A.d_val,
                            c.col, c.row, c.val);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            set_error(std::string("device CSS build: ") + hipGetErrorString(e));
-            (void)hipGetLastError();
-            return SPMV_ERROR_HIP;
-        }
+        SPMV_RETURN_IF(build_sync(st, "device CSS build"));
     }
     SPMV_RETURN_IF(css_finish(p, CL, A.m, A.n, A.nnz));
     SPMV_HIP_TRY(hipStreamSynchronize(st));

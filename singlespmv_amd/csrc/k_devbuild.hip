@@ -20,16 +20,12 @@
 #include <cstdlib>
 #include <vector>
 
+#include "build_util.hpp"
 #include "device.hpp"
-#include "internal.hpp"
 
 namespace spmv {
 
 namespace {
-
-inline unsigned grid_for(int64_t n, int per = 256) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per - 1) / per, 65536));
-}
 
 // ---- DIA census -------------------------------------------------------------
 // occ[col - row + m - 1] = 1 for every entry (benign byte races: all write 1)
@@ -219,44 +215,6 @@ __global__ __launch_bounds__(256) void coo_rows_kernel(const int64_t *__restrict
     }
 }
 
-// scratch freed on every exit path (after the stream drains)
-struct Scratch {
-    hipStream_t st;
-    std::vector<void *> v;
-    ~Scratch() {
-        (void)hipStreamSynchronize(st);
-        for (void *t : v) (void)hipFree(t);
-    }
-};
-
-template <typename T>
-int plan_alloc(spmv_plan_s *p, T **dst, int64_t count) {
-    void *q = nullptr;
-    SPMV_RETURN_IF(p->arena.alloc(&q, sizeof(T) * (size_t)std::max<int64_t>(count, 1)));
-    *dst = (T *)q;
-    return SPMV_SUCCESS;
-}
-
-// host array -> a new plan allocation (count elements; pad zeroed elements after)
-template <typename T>
-int plan_upload(spmv_plan_s *p, T **dst, const T *src, int64_t count, int64_t pad = 0) {
-    SPMV_RETURN_IF(plan_alloc(p, dst, count + pad));
-    if (count > 0) SPMV_HIP_TRY(hipMemcpyAsync(*dst, src, sizeof(T) * (size_t)count, hipMemcpyHostToDevice, p->stream));
-    if (pad > 0) SPMV_HIP_TRY(hipMemsetAsync(*dst + count, 0, sizeof(T) * (size_t)pad, p->stream));
-    return SPMV_SUCCESS;
-}
-
-int sync_or_error(spmv_plan_s *p, const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    if (e != hipSuccess) {
-        set_error(std::string(what) + ": " + hipGetErrorString(e));
-        (void)hipGetLastError();
-        return SPMV_ERROR_HIP;
-    }
-    return SPMV_SUCCESS;
-}
-
 // the ELL part (cap, order: JDS) of a plan from a device CSR
 int ell_fill_device(spmv_plan_s *p, const DevCsr &A, int cap, const int32_t *h_order, const int32_t *d_order) {
     EllDev &e = p->ell;
@@ -269,9 +227,9 @@ int ell_fill_device(spmv_plan_s *p, const DevCsr &A, int cap, const int32_t *h_o
     SPMV_RETURN_IF(plan_alloc(p, &e.col, total));
     SPMV_RETURN_IF(plan_alloc(p, &e.val, total));
     if (e.n_slices > 0 && total > 0)
-        hipLaunchKernelGGL(ell_fill_kernel, dim3((unsigned)((e.n_slices + 3) / 4)), dim3(256), 0, p->stream, A.d_rp,
+        hipLaunchKernelGGL(ell_fill_kernel, dim3(waves_grid(e.n_slices)), dim3(256), 0, p->stream, A.d_rp,
                            A.d_col, A.d_val, A.m, d_order, e.slice_off, e.n_slices, e.col, e.val);
-    SPMV_RETURN_IF(sync_or_error(p, "device ELL fill"));
+    SPMV_RETURN_IF(build_sync(p->stream, "device ELL fill"));
     ell_finish_info(p, maxw, total);
     return SPMV_SUCCESS;
 }
@@ -288,9 +246,9 @@ int overflow_device(spmv_plan_s *p, const DevCsr &A, int K) {
     SPMV_HIP_TRY(hipMemsetAsync(h.col + h.nnz, 0, sizeof(int32_t) * kPad, p->stream));
     SPMV_HIP_TRY(hipMemsetAsync(h.val + h.nnz, 0, sizeof(double) * kPad, p->stream));
     if (h.n_rows > 0)
-        hipLaunchKernelGGL(overflow_copy_kernel, dim3((unsigned)((h.n_rows + 3) / 4)), dim3(256), 0, p->stream, A.d_rp,
+        hipLaunchKernelGGL(overflow_copy_kernel, dim3(waves_grid(h.n_rows)), dim3(256), 0, p->stream, A.d_rp,
                            A.d_col, A.d_val, (int64_t)K, h.rows, h.row_ptr, h.n_rows, h.col, h.val);
-    return sync_or_error(p, "device overflow copy");
+    return build_sync(p->stream, "device overflow copy");
 }
 
 }  // namespace
@@ -303,16 +261,13 @@ int dia_offsets_device(spmv_plan_s *p, const DevCsr &A, int max_diags, double ma
     const int64_t N = A.m + A.n - 1;
     if (N <= 0) return SPMV_SUCCESS;
     const hipStream_t st = p->stream;
-    Scratch scratch{st, {}};
+    DevScratch sc(st);
     uint8_t *occ = nullptr;
-    SPMV_RETURN_IF(scratch_malloc(&occ, (size_t)N, "occ"));
-    scratch.v.push_back(occ);
     unsigned long long *cnt = nullptr;
-    SPMV_RETURN_IF(scratch_malloc(&cnt, sizeof(unsigned long long), "cnt"));
-    scratch.v.push_back(cnt);
     int32_t *out = nullptr;
-    SPMV_RETURN_IF(scratch_malloc(&out, sizeof(int32_t) * (size_t)(max_diags + 1), "out"));
-    scratch.v.push_back(out);
+    SPMV_RETURN_IF(sc.alloc(&occ, (size_t)N, "occ"));
+    SPMV_RETURN_IF(sc.alloc(&cnt, 1, "cnt"));
+    SPMV_RETURN_IF(sc.alloc(&out, (size_t)(max_diags + 1), "out"));
     SPMV_HIP_TRY(hipMemsetAsync(occ, 0, (size_t)N, st));
     SPMV_HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), st));
     if (A.m > 0 && A.nnz > 0)
@@ -334,10 +289,9 @@ int dia_offsets_device(spmv_plan_s *p, const DevCsr &A, int max_diags, double ma
 int rows_order_device(spmv_plan_s *p, const DevCsr &A, int *order) {
     *order = kRowsStrict;
     if (A.m == 0 || A.nnz == 0) return SPMV_SUCCESS;
-    Scratch scratch{p->stream, {}};
+    DevScratch sc(p->stream);
     unsigned long long *bad = nullptr, hb[2] = {0, 0};
-    SPMV_RETURN_IF(scratch_malloc(&bad, sizeof(hb), "bad"));
-    scratch.v.push_back(bad);
+    SPMV_RETURN_IF(sc.alloc(&bad, 2, "bad"));
     SPMV_HIP_TRY(hipMemsetAsync(bad, 0, sizeof(hb), p->stream));
     hipLaunchKernelGGL(rows_order_kernel, dim3(grid_for(A.m)), dim3(256), 0, p->stream, A.d_rp, A.d_col, A.m, bad);
     SPMV_HIP_TRY(hipGetLastError());
@@ -393,7 +347,7 @@ int build_dia_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o) {
             hipLaunchKernelGGL(dia_fill_kernel<false>, dim3(grid_for(A.m)), dim3(256), 0, p->stream, A.d_rp, A.d_col,
                                A.d_val, A.m, d.off, d.n_diags, off_min, span, (int64_t)d.group, nblk, d.val);
     }
-    SPMV_RETURN_IF(sync_or_error(p, "device DIA fill"));
+    SPMV_RETURN_IF(build_sync(p->stream, "device DIA fill"));
     if (!vmm_now) SPMV_RETURN_IF(dia_placement(p, A.m, A.n, vbytes, oo));
     dia_finish_info(p);
     return SPMV_SUCCESS;
@@ -442,7 +396,7 @@ int build_coo_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &) {
         SPMV_HIP_TRY(hipMemcpyAsync(c.val, A.d_val, sizeof(double) * (size_t)A.nnz, hipMemcpyDeviceToDevice, p->stream));
         hipLaunchKernelGGL(coo_rows_kernel, dim3(grid_for(A.m)), dim3(256), 0, p->stream, A.d_rp, A.m, c.row);
     }
-    SPMV_RETURN_IF(sync_or_error(p, "device COO build"));
+    SPMV_RETURN_IF(build_sync(p->stream, "device COO build"));
     coo_finish_info(p);
     return SPMV_SUCCESS;
 }
