@@ -5,6 +5,8 @@ Tolerances (BASELINE north star: within 1e-6 relative fp64):
 * every result must pass the reference VerifyResult criterion
   (src/util.cpp:67-83: a row fails iff abs > 1e-6 AND rel > 1e-6);
 * non-negative inputs: |y - y_ref| <= 1e-12 * |y_ref| + 1e-300 per row;
+  the golden fixtures, signed or not: <= 1e-12 * sum |a_ij x_j| + 1e-300
+  (signed data at every kernel path: tests/test_gpu_signed.py);
 * integer-valued inputs and sequential-order formats (ELL, DIA, 1-lane CSR,
   BIN): bit-exact against the oracle's sequential row sum -- BIN's long rows
   (the run path, plan info bin_long_len) excepted: deterministic, within
@@ -21,7 +23,9 @@ import pytest
 
 import oracle
 import singlespmv_amd as sp
+import signed_inputs as si
 from conftest import golden_names, load_golden
+from signed_inputs import with_empty_rows as _with_empty_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -94,18 +98,18 @@ def test_golden(name, fmt):
     A = sp.SpMat(m, n, g["row"], g["col"], g["val"])
     assert sp.verify_result(A, g["x"], y), "VerifyResult (1e-6) failed"
     yref = g["y_crs"]
-    signed = (g["val"] < 0).any() or (g["x"] < 0).any()
     if name == "syn_integer":
         assert np.array_equal(y, yref), "integer-valued inputs must be exact"
-    elif not signed:
-        check_close(y, yref, what=f"{name}/{fmt}")
+    # every fixture, signed or not: within 1e-12 of opt_crs relative to
+    # sum |a x| (= |y_ref| on non-negative inputs; |y_ref| itself says
+    # nothing once a row cancels)
+    mag = oracle_y(rp, g["col"], np.abs(g["val"]), np.abs(g["x"]))
+    err = np.abs(y - yref)
+    assert np.all(err <= REL * mag + 1e-300), f"{name}/{fmt} vs y_crs: {err.max()} (row {int(np.argmax(err - REL * mag))})"
     info = plan.info()
     # DIA adds duplicate entries into one slot first (src/opt_dia.cpp:47-56)
     dups = bool(np.any((np.diff(g["row"]) == 0) & (np.diff(g["col"]) == 0)))
-    sequential = info["format"] == "ell" or (info["format"] == "dia" and not dups) or (info["format"] == "csr" and info["csr_lanes"] == 1) \
-        or (info["format"] == "jds" and info["overflow_nnz"] == 0) \
-        or (info["format"] == "css" and info["css_split_rows"] == 0) \
-        or (info["format"] == "bin" and info["bin_long_len"] == 0)
+    sequential = si.plan_is_sequential(info, dia_duplicates=dups)
     if info["format"] == "bin":
         assert_bin_rows(plan, y, rp, g["col"], g["val"], g["x"], what=name)
     if sequential:
@@ -115,7 +119,6 @@ def test_golden(name, fmt):
     # 1e-12 of sum |a x| (their summation orders differ from each other)
     own = {"coo": ("y_coo",), "jds": ("y_jds",), "css": ("y_css",), "ss": ("y_ss_opt", "y_ss_pad"),
            "ell": ("y_ell",), "dia": ("y_dia",)}.get(fmt, ())
-    mag = oracle_y(rp, g["col"], np.abs(g["val"]), np.abs(g["x"]))
     for key in own:
         if key in g:
             err = np.abs(y - g[key])
@@ -645,18 +648,6 @@ def test_driver_binary_reports_block(fmt, name):
     assert (rec["Architecture"], rec["MatrixFormat"]) == ("GPU", name)
     assert (int(rec["nRow"]), int(rec["nCol"]), int(rec["nNnz"])) == (10, 10, 95)
     assert rec["Matrix"].startswith("random") and float(rec["Performance(GFLOPS)"]) > 0
-
-
-def _with_empty_rows(rp, col, val, frac, seed):
-    m = len(rp) - 1
-    rng = np.random.default_rng(seed)
-    lens = np.diff(rp)
-    zero = rng.random(m) < frac
-    zero[:3] = True
-    zero[-5:] = True
-    keep = np.repeat(~zero, lens)
-    rp2 = np.concatenate([[0], np.cumsum(np.where(zero, 0, lens))]).astype(np.int64)
-    return rp2, np.ascontiguousarray(col[keep]), np.ascontiguousarray(val[keep])
 
 
 def _device_csr(rp, col, val):
@@ -1647,3 +1638,80 @@ def test_crs_exact_skips_bin_for_rows_out_of_column_order():
     p.execute(x, y)
     assert np.array_equal(y, oracle_y(rp, col, val, x))
     p.destroy()
+
+
+def _crs_exact_plans(m, n, rp, col, val):
+    """(label, plan) of a CSR request under crs_exact from the host builder
+    and from a device CSR."""
+    yield "host", sp.Plan.from_csr(m, n, rp, col, val, "csr", crs_exact=True)
+    yield "device", sp.Plan.from_device_csr(m, n, *_device_csr(rp, col, val), fmt="csr", crs_exact=True)
+
+
+def test_crs_exact_keeps_bin_for_sorted_rows_with_duplicate_columns():
+    """Rows in ascending column order that hold duplicate columns still sum in
+    CSR order in BIN (a strip's entries keep their CSR order), so crs_exact
+    keeps BIN -- without the run path -- on the smallest shape AUTO's wide-x
+    rule sends there, from the host and from the device builder, and y is the
+    oracle's sequential sum bit for bit on cancelling values."""
+    m, n = 500_000, 800_000  # n * 8 > 6 MiB and nnz = 8 M
+    rp, col, _ = sp.generate_csr(sp.gen_spec("uniform", m, n=n, per_row=16, seed=33))
+    col = col.copy()
+    rng = np.random.default_rng(34)
+    rows = np.flatnonzero(rng.random(m) < 0.01)
+    at = rng.integers(0, 15, len(rows))
+    at[:50], at[50:100] = 0, 14  # pairs at the start and at the end of a row
+    j = rp[rows] + at
+    col[j + 1] = col[j]
+    # one pair on the last column of a 20 480-column strip
+    r = int(np.setdiff1d(np.arange(1000), rows)[0])
+    c = col[rp[r]:rp[r + 1]]
+    k = int(np.flatnonzero(np.diff(c // 20480) > 0)[0])
+    col[rp[r] + k] = col[rp[r] + k + 1] = (c[k + 1] // 20480) * 20480 - 1
+    inner = np.ones(len(col), bool)
+    inner[rp[:-1]] = False
+    d = np.diff(col, prepend=0)[inner]
+    assert (d >= 0).all() and (d == 0).sum() >= len(rows) + 1  # sorted, with duplicates
+    val, x = si.cancel(rp, col, n, seed=35)
+    yo = oracle_y(rp, col, val, x)
+    digests = []
+    for label, p in _crs_exact_plans(m, n, rp, col, val):
+        info = p.info()
+        assert info["format"] == "bin", (label, info["format"])
+        # crs_exact sets the option bin_long_len = -1; plan info reports the threshold in use, 0 = no run path
+        assert info["bin_long_len"] == 0 and info["bin_long_rows"] == 0, label
+        assert p.built_on_device() == (label == "device")
+        digests.append(p.digest())
+        y = np.full(m, np.nan)
+        p.execute(x, y)
+        assert np.array_equal(y, yo), f"{label}: crs_exact BIN differs from the sequential sum"
+        p.destroy()
+    assert digests[0] == digests[1], [a for a in digests[0] if digests[0][a] != digests[1].get(a)]
+
+
+def test_crs_exact_skips_dia_for_rows_with_duplicate_columns():
+    """DIA adds duplicate entries into one slot before the product, which is
+    not the sequential sum: crs_exact takes DIA only for strictly ascending
+    rows.  The banded matrix gives DIA and the oracle's y bit for bit; with a
+    few duplicated columns it gets another sequential layout, same exactness,
+    from the host and from the device builder."""
+    m, n, rp, col = si.structure("banded")
+    rp, col = rp.copy(), col.copy()  # the shared arrays are read-only
+    val, x = si.cancel(rp, col, n, seed=36)
+    for label, p in _crs_exact_plans(m, n, rp, col, val):
+        assert p.info()["format"] == "dia", (label, p.info()["format"])
+        y = np.full(m, np.nan)
+        p.execute(x, y)
+        assert np.array_equal(y, oracle_y(rp, col, val, x)), label
+        p.destroy()
+    col2 = col.copy()
+    for r, k in ((0, 0), (1, 39), (777, 40), (m // 2, 79), (m - 1, 20)):  # first / last / inner pairs, clipped rows too
+        col2[rp[r] + k + 1] = col2[rp[r] + k]
+    val2, x2 = si.cancel(rp, col2, n, seed=37)
+    yo = oracle_y(rp, col2, val2, x2)
+    for label, p in _crs_exact_plans(m, n, rp, col2, val2):
+        info = p.info()
+        assert info["format"] != "dia" and si.plan_is_sequential(info), (label, info["format"])
+        y = np.full(m, np.nan)
+        p.execute(x2, y)
+        assert np.array_equal(y, yo), f"{label}: {info['format']} under crs_exact differs from the sequential sum"
+        p.destroy()
