@@ -38,6 +38,24 @@
  * plan creation and never mutated (unlike the CSR5 handle, which transposes
  * the caller's arrays in place, CSR5_cuda/anonymouslib_cuda.h:203-204).
  *
+ * Non-finite and subnormal values: every product and every sum is an IEEE
+ * binary64 operation, round to nearest, with gradual underflow -- nothing is
+ * flushed to zero, the LDS (ds_add_f64) and global (global_atomic_add_f64)
+ * atomic adds of BIN, CSS and COO included -- and stored zeros are multiplied
+ * like any other entry (0 * Inf = NaN).  A non-finite x[c] therefore makes
+ * non-finite exactly the rows that reference column c in CSR (every kernel),
+ * SS, COO, CSS and BIN, with the class (NaN, +Inf, -Inf) the sequential sum
+ * gives; every other row is bit for bit what it is for a finite x[c]: masked
+ * lanes, tile and unit padding and dummy slots are dropped by selects, never
+ * by a zero weight.  The padded layouts multiply 0 by a few more x entries:
+ * ELL, JDS and HYB pad a row with its last real column (their 0 * x[c] turns
+ * the row's +-Inf into NaN) and an empty row with column 0 (NaN instead of 0
+ * where x[0] is not finite and the row's slice has any width); DIA reads x[clamp(r + off, 0, n - 1)] for every
+ * stored diagonal off of row r.  This is the caveat noted at
+ * spmv_options_t.crs_exact, stated here once for every layout.  Finite terms
+ * whose partial sum overflows give a result that depends on the add order,
+ * hence on the format.  (tests/test_gpu_special.py.)
+ *
  * Threading: thread-compatible.  One plan per thread; a plan may be used from
  * any thread but not concurrently.
  */
