@@ -76,7 +76,9 @@ extern "C" {
  * size) and appended bin_sum_entries to spmv_plan_info_t.  crs_exact and build
  * (round 5) took the last reserved words: same size, and 0
  * (spmv_options_default) keeps the version-3 results (build = AUTO moves only
- * where the layout is made, not what it is).  Callers may
+ * where the layout is made, not what it is).  The multi-vector entry points
+ * (spmv_execute_multi, spmv_time_multi, spmv_multi_path) are new functions
+ * and change no struct: the version stays 3.  Callers may
  * check spmv_api_version() == SPMV_HIP_API_VERSION once at startup; the
  * structs are only ever filled by spmv_options_default / spmv_plan_info of a
  * library with the same version. */
@@ -339,6 +341,56 @@ int spmv_set_stream(spmv_plan_t plan, void *hip_stream);
  * hipEvents recorded on the plan's stream; *ms = elapsed milliseconds total. */
 int spmv_time(spmv_plan_t plan, const double *x_dev, double *y_dev, int32_t iters,
               double *ms);
+
+/* ---- multi-vector execute: Y = A X for k right-hand sides -----------------
+ * Y[:, j] = A * X[:, j] for j in [0, k).  X and Y are row-major
+ * ("interleaved") blocks: x_j[i] = X[i*ldx + j] (n rows), y_j[r] =
+ * Y[r*ldy + j] (m rows), ldx >= k, ldy >= k.  beta = 0: the k used columns of
+ * every row of Y are overwritten; columns [k, ldy) of Y are never written and
+ * columns [k, ldx) of X are never read.  X and Y must not overlap.
+ *
+ * Per-column semantics: column j of Y depends on column j of X only and is,
+ * bit for bit, what spmv_execute gives for that vector on this plan (COO:
+ * within its atomics' order).  A NaN or Inf anywhere in column j' != j never
+ * reaches column j; the non-finite rules of this header's opening comment
+ * hold per column.
+ *
+ * Flags: SPMV_X_DEVICE, SPMV_Y_DEVICE and SPMV_ASYNC as for spmv_execute.
+ * Host blocks are staged through plan-owned device buffers (hipMemcpy2DAsync;
+ * only the k used columns travel) at a pitch of k rounded up to even.
+ * SPMV_X_STAGED / SPMV_Y_STAGED, k < 1, k > SPMV_MULTI_MAX, ldx < k, ldy < k
+ * and a NULL X or Y (with n, m > 0) return SPMV_ERROR_INVALID_VALUE before
+ * any device work.  A multi execute clears the mark spmv_fetch_y needs, like
+ * any other non-staged execute.
+ *
+ * Paths.  k is cut greedily into blocks of 8, 4 and 2 columns, then single
+ * columns (block starts are even).  A block of width K >= 2 is ONE fused
+ * launch -- the matrix is streamed once for K vectors -- when the plan is DIA,
+ * ELL, or JDS without overflow rows, the block's X and Y addresses are
+ * 16-byte aligned and ldx and ldy are even.  Every other block goes column by
+ * column through the generic path, which serves every format: the column is
+ * packed into a contiguous scratch vector (n + m doubles, allocated by the
+ * first call that needs it; SPMV_ERROR_OUT_OF_MEMORY leaves the plan usable),
+ * the plan's single-vector kernels run, and the result is written back into
+ * its column (ld = 1: read / written in place).  The drop-in, the CSR5
+ * handle, spmv_dist_*, HIP graphs and spmv_profile have no multi form. */
+#define SPMV_MULTI_MAX 32
+int spmv_execute_multi(spmv_plan_t plan, int32_t k, const double *X, int64_t ldx,
+                       double *Y, int64_t ldy, uint32_t flags);
+
+/* iters back-to-back device-resident multi executes between two events on
+ * the plan's stream (the multi counterpart of spmv_time). */
+int spmv_time_multi(spmv_plan_t plan, int32_t k, const double *X_dev, int64_t ldx,
+                    double *Y_dev, int64_t ldy, int32_t iters, double *ms);
+
+/* How the call above would be cut: widths[b] >= 2 is one fused launch over
+ * that many consecutive columns, widths[b] == 1 is one column through the
+ * generic path; the widths sum to k.  *n_blocks = the number of blocks
+ * (widths beyond `cap` are not written).  A check and a documentation aid,
+ * not a compute path. */
+int spmv_multi_path(spmv_plan_t plan, int32_t k, const double *X, int64_t ldx,
+                    const double *Y, int64_t ldy, uint32_t flags,
+                    int32_t *widths, int32_t cap, int32_t *n_blocks);
 
 /* ---- HIP graph of the device-resident execute -----------------------------
  * The plan's launch sequence for (x_dev -> y_dev), captured `reps` times in a

@@ -109,6 +109,7 @@ EXPORTS = [
     "spmv_mixed_probe", "spmv_graph_create", "spmv_graph_launch", "spmv_graph_time", "spmv_graph_destroy",
     "spmv_plan_digest", "spmv_plan_digest_name", "spmv_dist_shard", "spmv_dist_assemble",
     "spmv_fetch_y", "spmv_dist_fetch_y", "spmv_plan_built_on_device",
+    "spmv_execute_multi", "spmv_time_multi", "spmv_multi_path",
 ]
 
 _lib = None
@@ -143,6 +144,9 @@ def lib():
     L.spmv_execute.argtypes = [vp, vp, vp, C.c_uint32]
     L.spmv_execute_alpha.argtypes = [vp, f64, vp, vp, C.c_uint32]
     L.spmv_fetch_y.argtypes = [vp, vp]
+    L.spmv_execute_multi.argtypes = [vp, i32, vp, i64, vp, i64, C.c_uint32]
+    L.spmv_time_multi.argtypes = [vp, i32, vp, i64, vp, i64, i32, C.POINTER(f64)]
+    L.spmv_multi_path.argtypes = [vp, i32, vp, i64, vp, i64, C.c_uint32, C.POINTER(i32), i32, C.POINTER(i32)]
     L.spmv_dist_fetch_y.argtypes = [vp, vp]
     L.spmv_plan_create_csr32_device.argtypes = [i32, i32, i32, vp, vp, vp, C.POINTER(Options), C.POINTER(vp)]
     L.spmv_set_stream.argtypes = [vp, vp]
@@ -426,6 +430,48 @@ def _check_vec(a, length: int, name: str, device: int, writable: bool) -> None:
     raise ValueError(f"{name} must be a numpy array or a torch tensor (raw addresses: use the C-ABI)")
 
 
+MULTI_MAX = 32  # SPMV_MULTI_MAX
+
+
+def _check_block(a, rows: int, name: str, device: int, writable: bool):
+    """A 2-D block handed to the multi-vector C-ABI: float64, `rows` rows,
+    1..MULTI_MAX columns with unit stride along a row and a row stride (ld)
+    of at least the column count -- a view X[:, :k] of a wider C-contiguous
+    array qualifies.  Returns (k, ld).  Raises ValueError instead of letting
+    the kernels or the copies run past the block."""
+    if isinstance(a, np.ndarray):
+        if a.dtype != np.float64:
+            raise ValueError(f"{name} must be float64, got {a.dtype}")
+        if writable and not a.flags.writeable:
+            raise ValueError(f"{name} is read-only")
+        shape, strides = a.shape, [s // 8 if s % 8 == 0 else -1 for s in a.strides]
+    elif torch is not None and isinstance(a, torch.Tensor):
+        if a.dtype != torch.float64:
+            raise ValueError(f"{name} must be torch.float64, got {a.dtype}")
+        if not a.is_cuda:
+            raise ValueError(f"{name}: pass CPU data as a numpy array (host buffer)")
+        if a.device.index != device:
+            raise ValueError(f"{name} is on cuda:{a.device.index}, the plan on cuda:{device}")
+        shape, strides = tuple(a.shape), list(a.stride())
+    else:
+        raise ValueError(f"{name} must be a 2-D numpy array or torch tensor (raw addresses: use the C-ABI)")
+    if len(shape) != 2:
+        raise ValueError(f"{name} must be 2-D (rows x k), got {len(shape)} dimensions")
+    if shape[0] != rows:
+        raise ValueError(f"{name} has {shape[0]} rows, the plan needs {rows}")
+    k = shape[1]
+    if not 1 <= k <= MULTI_MAX:
+        raise ValueError(f"{name} has {k} columns, supported: 1..{MULTI_MAX}")
+    if rows == 0:  # no element: the strides of an empty array mean nothing
+        return k, k
+    if k > 1 and strides[1] != 1:
+        raise ValueError(f"{name} must have unit stride along its columns (row-major block)")
+    ld = strides[0] if rows > 1 else max(strides[0], k)
+    if ld < k:
+        raise ValueError(f"{name}: row stride {ld} is below its {k} columns")
+    return k, ld
+
+
 class Graph:
     """An instantiated HIP graph of `reps` executes of one plan (spmv_graph_*)."""
 
@@ -527,6 +573,48 @@ class Plan:
         else:
             _check(lib().spmv_execute_alpha(self._h, float(alpha), _ptr(x), _ptr(y), flags),
                    "spmv_execute_alpha")
+
+    def _check_blocks(self, X, Y):
+        k, ldx = _check_block(X, self.n, "X", self.device, writable=False)
+        ky, ldy = _check_block(Y, self.m, "Y", self.device, writable=True)
+        if k != ky:
+            raise ValueError(f"X has {k} columns, Y {ky}")
+        flags = (X_DEVICE if _is_device(X) else 0) | (Y_DEVICE if _is_device(Y) else 0)
+        return k, ldx, ldy, flags
+
+    def execute_multi(self, X, Y, async_: bool = False) -> None:
+        """Y[:, j] = A X[:, j] for the k columns of the 2-D blocks X (n x k)
+        and Y (m x k) in one call (spmv_execute_multi).  Row-major blocks with
+        unit stride along a row; the row stride may exceed k (a view
+        X[:, :k] of a wider array): the columns beyond k are neither read nor
+        written.  numpy arrays are host buffers, torch CUDA tensors device
+        buffers."""
+        k, ldx, ldy, flags = self._check_blocks(X, Y)
+        if async_:
+            flags |= ASYNC
+        _check(lib().spmv_execute_multi(self._h, k, _ptr(X), ldx, _ptr(Y), ldy, flags), "spmv_execute_multi")
+
+    def time_multi(self, X_dev, Y_dev, iters: int) -> float:
+        """Milliseconds for `iters` back-to-back multi executes (HIP events on
+        the plan's stream)."""
+        k, ldx, ldy, _ = self._check_blocks(X_dev, Y_dev)
+        if not (_is_device(X_dev) or self.n == 0) or not (_is_device(Y_dev) or self.m == 0):
+            raise ValueError("time_multi() needs device tensors for X and Y")
+        ms = C.c_double()
+        _check(lib().spmv_time_multi(self._h, k, _ptr(X_dev), ldx, _ptr(Y_dev), ldy, iters, C.byref(ms)),
+               "spmv_time_multi")
+        return ms.value
+
+    def multi_path(self, X, Y) -> list:
+        """How execute_multi(X, Y) is cut (spmv_multi_path): a width >= 2 is
+        one fused launch over that many consecutive columns, a 1 one column
+        through the generic path."""
+        k, ldx, ldy, flags = self._check_blocks(X, Y)
+        w = (C.c_int32 * MULTI_MAX)()
+        nb = C.c_int32()
+        _check(lib().spmv_multi_path(self._h, k, _ptr(X), ldx, _ptr(Y), ldy, flags, w, MULTI_MAX, C.byref(nb)),
+               "spmv_multi_path")
+        return [int(w[b]) for b in range(nb.value)]
 
     def __call__(self, x, y=None):
         if y is None:

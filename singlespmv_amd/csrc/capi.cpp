@@ -543,6 +543,205 @@ int spmv_time(spmv_plan_t p, const double *x_dev, double *y_dev, int32_t iters, 
 
 }  // extern "C"
 
+// ---- multi-vector execute (Y = A X, k interleaved right-hand sides) ---------
+namespace spmv {
+
+// Widths with a fused kernel, per format, widest first.  Every width of
+// k_multi.hip that beat K single-vector executes on the same plan is listed
+// (DESIGN §3.7); a width that is not listed is cut narrower.
+static const int kMultiWidthsDia[] = {8, 4, 2};
+static const int kMultiWidthsEll[] = {8, 4, 2};
+
+static bool multi_format_fused(const spmv_plan_s *p) {
+    if (p->format == SPMV_FORMAT_DIA || p->format == SPMV_FORMAT_ELL) return true;
+    // JDS: the sliced-ELL part alone; overflow rows (a second kernel adding
+    // into y) take the generic path, as HYB does
+    return p->format == SPMV_FORMAT_JDS && p->hyb.nnz == 0 && p->hyb.n_rows == 0;
+}
+
+static bool multi_width_listed(const spmv_plan_s *p, int w) {
+    const int *tab = p->format == SPMV_FORMAT_DIA ? kMultiWidthsDia : kMultiWidthsEll;
+    for (int i = 0; i < 3; ++i)
+        if (tab[i] == w) return true;
+    return false;
+}
+
+// The cut of k columns: greedily 8, 4, 2 (the listed widths), then single
+// columns -- block starts are even.  A block is fused when the format has a
+// kernel, its X and Y block addresses are 16-byte aligned and ldx, ldy are
+// even; else each of its columns is a width-1 block of the generic path.
+static void multi_cut(const spmv_plan_s *p, int32_t k, uintptr_t x_addr, int64_t ldx, uintptr_t y_addr, int64_t ldy,
+                      std::vector<int32_t> &widths) {
+    widths.clear();
+    const bool fmt = multi_format_fused(p);
+    const bool even = ldx % 2 == 0 && ldy % 2 == 0;
+    int32_t j = 0;
+    while (j < k) {
+        int w = 1;
+        for (int c : {8, 4, 2})
+            if (k - j >= c && (!fmt || multi_width_listed(p, c))) {
+                w = c;
+                break;
+            }
+        const bool fused = w >= 2 && fmt && even && ((x_addr + sizeof(double) * (size_t)j) & 15) == 0 &&
+                           ((y_addr + sizeof(double) * (size_t)j) & 15) == 0;
+        if (fused) widths.push_back(w);
+        else widths.insert(widths.end(), (size_t)w, 1);
+        j += w;
+    }
+}
+
+static int multi_check_args(int32_t k, const double *X, int64_t ldx, const double *Y, int64_t ldy, uint32_t flags) {
+    (void)X;
+    (void)Y;
+    SPMV_CHECK_ARG(!(flags & (SPMV_X_STAGED | SPMV_Y_STAGED)),
+                   "multi execute: SPMV_X_STAGED / SPMV_Y_STAGED are not supported");
+    SPMV_CHECK_ARG(k >= 1 && k <= SPMV_MULTI_MAX, "multi execute: k outside [1, SPMV_MULTI_MAX]");
+    SPMV_CHECK_ARG(ldx >= k, "multi execute: ldx < k");
+    SPMV_CHECK_ARG(ldy >= k, "multi execute: ldy < k");
+    return SPMV_SUCCESS;
+}
+
+// the column scratch of the generic path: n + m doubles of plain hipMalloc
+// memory (COO adds into it with f64 atomics), allocated at the first use
+static int multi_scratch(spmv_plan_s *p) {
+    if (p->m_scratch) return SPMV_SUCCESS;
+    const size_t keep = p->arena.vmm_min;
+    p->arena.vmm_min = 0;
+    void *q = nullptr;
+    const int st = p->arena.alloc(&q, sizeof(double) * (size_t)std::max<int64_t>(p->n + p->m, 1));
+    p->arena.vmm_min = keep;
+    SPMV_RETURN_IF(st);
+    p->m_scratch = (double *)q;
+    return SPMV_SUCCESS;
+}
+
+// the launches of one multi execute on device blocks, on p->stream
+static int multi_dispatch(spmv_plan_s *p, int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy) {
+    if (p->m == 0) return SPMV_SUCCESS;
+    std::vector<int32_t> widths;
+    multi_cut(p, k, reinterpret_cast<uintptr_t>(X), ldx, reinterpret_cast<uintptr_t>(Y), ldy, widths);
+    int32_t j = 0;
+    for (const int32_t w : widths) {
+        if (w >= 2) {
+            if (p->format == SPMV_FORMAT_DIA) SPMV_RETURN_IF(launch_dia_multi(p, w, X + j, ldx, Y + j, ldy));
+            else SPMV_RETURN_IF(launch_ell_multi(p, w, X + j, ldx, Y + j, ldy));
+        } else {
+            // a contiguous column (ld = 1, hence k = 1) is read / written in place
+            const double *xs = X;
+            double *ys = Y;
+            if (ldx != 1 || ldy != 1) SPMV_RETURN_IF(multi_scratch(p));
+            if (ldx != 1) {
+                SPMV_RETURN_IF(launch_multi_copy(p, p->n, X + j, ldx, p->m_scratch, 1));
+                xs = p->m_scratch;
+            }
+            if (ldy != 1) ys = p->m_scratch + p->n;
+            SPMV_RETURN_IF(dispatch(p, xs, ys));
+            if (ldy != 1) SPMV_RETURN_IF(launch_multi_copy(p, p->m, ys, 1, Y + j, ldy));
+        }
+        j += w;
+    }
+    return SPMV_SUCCESS;
+}
+
+// a host staging block of at least `need` doubles
+static int multi_stage(spmv_plan_s *p, double **buf, int64_t *cap, int64_t need) {
+    if (*buf && *cap >= need) return SPMV_SUCCESS;
+    if (*buf) p->arena.free(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    void *q = nullptr;
+    SPMV_RETURN_IF(p->arena.alloc(&q, sizeof(double) * (size_t)std::max<int64_t>(need, 1)));
+    *buf = (double *)q;
+    *cap = need;
+    return SPMV_SUCCESS;
+}
+
+}  // namespace spmv
+
+extern "C" {
+
+int spmv_execute_multi(spmv_plan_t p, int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy,
+                       uint32_t flags) {
+    SPMV_RETURN_IF(multi_check_args(k, X, ldx, Y, ldy, flags));
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    SPMV_CHECK_ARG((X != nullptr || p->n == 0) && (Y != nullptr || p->m == 0), "multi execute: X or Y is NULL");
+    SPMV_RETURN_IF(bind_device(p));
+    p->y_staged = false;  // like any other non-staged execute (spmv_fetch_y)
+    const int64_t kp = (k + 1) & ~1;  // staging pitch: host callers always qualify for the fused path
+    const double *dX = X;
+    double *dY = Y;
+    int64_t dldx = ldx, dldy = ldy;
+    if (!(flags & SPMV_X_DEVICE)) {
+        SPMV_RETURN_IF(multi_stage(p, &p->mx_stage, &p->mx_cap, p->n * kp));
+        if (p->n)
+            SPMV_HIP_TRY(hipMemcpy2DAsync(p->mx_stage, sizeof(double) * kp, X, sizeof(double) * ldx,
+                                          sizeof(double) * k, (size_t)p->n, hipMemcpyHostToDevice, p->stream));
+        dX = p->mx_stage;
+        dldx = kp;
+    }
+    if (!(flags & SPMV_Y_DEVICE)) {
+        SPMV_RETURN_IF(multi_stage(p, &p->my_stage, &p->my_cap, p->m * kp));
+        dY = p->my_stage;
+        dldy = kp;
+    }
+    SPMV_RETURN_IF(multi_dispatch(p, k, dX, dldx, dY, dldy));
+    if (!(flags & SPMV_Y_DEVICE)) {
+        if (p->m)
+            SPMV_HIP_TRY(hipMemcpy2DAsync(Y, sizeof(double) * ldy, dY, sizeof(double) * kp, sizeof(double) * k,
+                                          (size_t)p->m, hipMemcpyDeviceToHost, p->stream));
+        SPMV_HIP_TRY(hipStreamSynchronize(p->stream));
+    } else if (!(flags & SPMV_ASYNC) || !(flags & SPMV_X_DEVICE)) {
+        SPMV_HIP_TRY(hipStreamSynchronize(p->stream));
+    }
+    return SPMV_SUCCESS;
+}
+
+int spmv_multi_path(spmv_plan_t p, int32_t k, const double *X, int64_t ldx, const double *Y, int64_t ldy,
+                    uint32_t flags, int32_t *widths, int32_t cap, int32_t *n_blocks) {
+    SPMV_RETURN_IF(multi_check_args(k, X, ldx, Y, ldy, flags));
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    SPMV_CHECK_ARG(n_blocks != nullptr && (widths != nullptr || cap <= 0), "n_blocks or widths is NULL");
+    // host blocks are staged at an aligned base with pitch k rounded up to even
+    const int64_t kp = (k + 1) & ~1;
+    const bool xd = (flags & SPMV_X_DEVICE) != 0, yd = (flags & SPMV_Y_DEVICE) != 0;
+    std::vector<int32_t> w;
+    multi_cut(p, k, xd ? reinterpret_cast<uintptr_t>(X) : 0, xd ? ldx : kp, yd ? reinterpret_cast<uintptr_t>(Y) : 0,
+              yd ? ldy : kp, w);
+    *n_blocks = (int32_t)w.size();
+    for (int32_t b = 0; b < *n_blocks && b < cap; ++b) widths[b] = w[b];
+    return SPMV_SUCCESS;
+}
+
+int spmv_time_multi(spmv_plan_t p, int32_t k, const double *X_dev, int64_t ldx, double *Y_dev, int64_t ldy,
+                    int32_t iters, double *ms) {
+    SPMV_RETURN_IF(multi_check_args(k, X_dev, ldx, Y_dev, ldy, 0));
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    SPMV_CHECK_ARG(ms != nullptr && iters > 0, "ms is NULL or iters < 1");
+    SPMV_CHECK_ARG((X_dev != nullptr || p->n == 0) && (Y_dev != nullptr || p->m == 0), "multi execute: X or Y is NULL");
+    SPMV_RETURN_IF(bind_device(p));
+    p->y_staged = false;
+    // both events are destroyed on every path
+    hipEvent_t a = nullptr, b = nullptr;
+    hipError_t e = hipEventCreate(&a);
+    if (e == hipSuccess) e = hipEventCreate(&b);
+    if (e == hipSuccess) e = hipEventRecord(a, p->stream);
+    int st = SPMV_SUCCESS;
+    for (int i = 0; i < iters && st == SPMV_SUCCESS && e == hipSuccess; ++i)
+        st = multi_dispatch(p, k, X_dev, ldx, Y_dev, ldy);
+    if (e == hipSuccess) e = hipEventRecord(b, p->stream);
+    if (e == hipSuccess) e = hipEventSynchronize(b);
+    float f = 0;
+    if (e == hipSuccess) e = hipEventElapsedTime(&f, a, b);
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+    SPMV_HIP_TRY(e);
+    *ms = f;
+    return st;
+}
+
+}  // extern "C"
+
 struct spmv_graph_s {
     spmv_plan_t plan = nullptr;  // launches use the plan's stream; destroy does not touch it
     int device = 0;              // the plan's device, for destroy

@@ -441,6 +441,11 @@ struct spmv_plan_s {
     double *x_stage = nullptr;  // host-x staging (opt_cusparse.cpp:44-45)
     double *y_stage = nullptr;
     bool y_staged = false;      // y_stage holds the y of an SPMV_Y_STAGED execute
+    // spmv_execute_multi: host X / Y staging blocks (pitch = k rounded up to
+    // even) and the generic path's column scratch (n + m doubles, plain hipMalloc)
+    double *mx_stage = nullptr, *my_stage = nullptr;
+    int64_t mx_cap = 0, my_cap = 0;  // doubles
+    double *m_scratch = nullptr;
     int64_t stored_slots = 0;
     int64_t empty_rows = 0;
     int64_t algo_bytes = 0;
@@ -611,5 +616,13 @@ int launch_css(const spmv_plan_s *p, const double *x, double *y);
 int launch_coo(const spmv_plan_s *p, const double *x, double *y);
 int launch_bin(const spmv_plan_s *p, const double *x, double *y);
 int bin_time_mul(const spmv_plan_s *p, const double *x, float *ms);  // one timed Mul pass (build-time)
+// k_multi.hip -- K interleaved right-hand sides (x_j[i] = X[i*ldx + j]): the fused
+// DIA / sliced-ELL kernels (K = 2, 4, 8; X, Y 16-byte aligned, ldx, ldy even)
+// and the strided copies / zero fill of the generic path
+int launch_dia_multi(const spmv_plan_s *p, int K, const double *X, int64_t ldx, double *Y, int64_t ldy);
+int launch_ell_multi(const spmv_plan_s *p, int K, const double *X, int64_t ldx, double *Y, int64_t ldy);
+int launch_multi_copy(const spmv_plan_s *p, int64_t len, const double *src, int64_t src_ld, double *dst,
+                      int64_t dst_ld);
+int launch_multi_zero(const spmv_plan_s *p, int32_t k, double *Y, int64_t ldy);
 
 }  // namespace spmv
