@@ -269,9 +269,14 @@ int spmv_plan_destroy(spmv_plan_t plan);
  * of src/util.cpp:16-18, src/util.h:59-65 and the Mul/Sum split printed by
  * src/main.cpp:172-175).  Runs `iters` synchronised calls on device x/y and
  * returns the mean ms of each phase of the plan's launch sequence:
- *   CSR "csr" | ELL, JDS "ell" | HYB "ell","overflow" | SS "tile","fixup" |
+ *   CSR "csr" | ELL "ell" | JDS, HYB "ell","overflow" | SS "tile","fixup" |
  *   DIA "dia" | CSS "sweep" | COO "zero_y","segment" | BIN "mul","sum"
- *   (repeated per row group). */
+ * JDS and HYB report the "overflow" phase even when no row overflows (then
+ * it times no launch).  BIN has two phases whatever bin_groups is: the row
+ * groups' Mul launches are one phase, their one Sum launch the other (only
+ * the probe build's per-group product buffer, an experiment switch the
+ * product library ignores, numbers a "mul.g","sum.g" pair per group).
+ * spmv_phase_name(plan, k) names phase k, "" for k outside [0, n_phases). */
 int spmv_profile(spmv_plan_t plan, const double *x_dev, double *y_dev, int32_t iters,
                  double *phase_ms, int32_t max_phases, int32_t *n_phases);
 const char *spmv_phase_name(spmv_plan_t plan, int32_t k);
@@ -320,6 +325,17 @@ int spmv_lds_order_probe(int32_t device, int32_t rounds, const int32_t *slot, co
                               to the host when the caller reads it -- the
                               per-call 8m-byte download of opt_cusparse
                               (src/opt_cusparse.cpp:82) leaves the timed loop */
+
+/* Buffer contract of device x and y (tests/test_gpu_routes.py pins it on
+ * guarded buffers for every format): x and y need the 8-byte alignment of a
+ * double, no more -- a view one double into a 16-byte-aligned allocation is
+ * as good as its base, and gives the same y bit for bit (DIA stores row pairs
+ * as 16 bytes only where y is 16-byte aligned, BIN stages x by LDS-DMA only
+ * where x is).  Nothing outside [x, x + n) influences y (padded slots
+ * multiply 0 by an entry inside the range), and nothing outside [y, y + m)
+ * is written.  This holds for spmv_execute, spmv_execute_alpha, spmv_time,
+ * spmv_profile, spmv_graph_* and the k = 1, ldx = ldy = 1 case of
+ * spmv_execute_multi, which runs the plan's kernels in place on X and Y. */
 
 /* y = A * x.  x holds n doubles, y holds m doubles. */
 int spmv_execute(spmv_plan_t plan, const double *x, double *y, uint32_t flags);
