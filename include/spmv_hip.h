@@ -335,7 +335,9 @@ int spmv_lds_order_probe(int32_t device, int32_t rounds, const int32_t *slot, co
  * multiply 0 by an entry inside the range), and nothing outside [y, y + m)
  * is written.  This holds for spmv_execute, spmv_execute_alpha, spmv_time,
  * spmv_profile, spmv_graph_* and the k = 1, ldx = ldy = 1 case of
- * spmv_execute_multi, which runs the plan's kernels in place on X and Y. */
+ * spmv_execute_multi, which runs the plan's kernels in place on X and Y.
+ * n may be anything below 2^31 - 1: an x of 4 GiB and more (n >= 2^29) takes
+ * 64-bit offsets in every format (tests/test_gpu_wide_x.py). */
 
 /* y = A * x.  x holds n doubles, y holds m doubles. */
 int spmv_execute(spmv_plan_t plan, const double *x, double *y, uint32_t flags);

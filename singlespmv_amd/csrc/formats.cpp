@@ -761,6 +761,14 @@ static bool dia_offsets(const HostCsr &A, int max_diags, double max_fill, std::v
     for (int64_t r = 0; r < A.m; ++r)
         for (int64_t j = A.row_ptr[r]; j < A.row_ptr[r + 1]; ++j) occ[(size_t)(A.col[j] - r + A.m - 1)] = 1;
     for (int64_t d = 0; d < N; ++d) {
+        if (d + 8 <= N) {  // eight empty diagonals at a time (n near 2^31: 2^31 of them)
+            uint64_t w;
+            std::memcpy(&w, &occ[(size_t)d], sizeof(w));
+            if (!w) {
+                d += 7;
+                continue;
+            }
+        }
         if (occ[(size_t)d]) {
             offs.push_back((int32_t)(d - (A.m - 1)));
             if ((int)offs.size() > max_diags) return false;
@@ -890,9 +898,19 @@ int build_dia(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o) {
     }
     d.n_diags = (int)offs.size();
     d.off_host = offs;
-    const int64_t N = A.m + A.n - 1;
-    std::vector<int32_t> idx((size_t)std::max<int64_t>(N, 1), -1);
-    for (int i = 0; i < d.n_diags; ++i) idx[(size_t)(offs[i] + A.m - 1)] = i;
+    // offset -> diagonal: a table over [offs.front(), offs.back()] while that
+    // span is small (a band), else a binary search -- never a table over all
+    // m + n - 1 offsets (8 GB of host memory at n = 2^31 for two far bands)
+    const int64_t off0 = offs.empty() ? 0 : offs.front();
+    const int64_t span = offs.empty() ? 0 : (int64_t)offs.back() - off0 + 1;
+    const bool lut = span <= ((int64_t)1 << 24);
+    std::vector<int32_t> idx(lut ? (size_t)span : 0, -1);
+    if (lut)
+        for (int i = 0; i < d.n_diags; ++i) idx[(size_t)(offs[i] - off0)] = i;
+    auto diag_of = [&](int64_t off) -> int {
+        if (lut) return idx[(size_t)(off - off0)];
+        return (int)(std::lower_bound(offs.begin(), offs.end(), (int32_t)off) - offs.begin());
+    };
     // row blocks of kDiaBlockRows (one workgroup), each holding its rows of
     // every diagonal contiguously: val[(blk*nd + d)*B + r%B]
     d.mp = round_up(A.m, kDiaBlockRows);
@@ -904,7 +922,7 @@ int build_dia(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o) {
 #pragma omp parallel for schedule(static)
     for (int64_t r = 0; r < A.m; ++r)
         for (int64_t j = A.row_ptr[r]; j < A.row_ptr[r + 1]; ++j) {
-            const int di = idx[(size_t)(A.col[j] - r + A.m - 1)];
+            const int di = diag_of((int64_t)A.col[j] - r);
             const int64_t b = r / kDiaBlockRows;
             int64_t at = (b * nd + di) * kDiaBlockRows + r % kDiaBlockRows;
             if (G > 0) {  // interleaved groups (k_dia.hip)
