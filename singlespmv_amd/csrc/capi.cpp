@@ -329,6 +329,7 @@ static int dispatch(const spmv_plan_s *p, const double *x, double *y) {
         case SPMV_FORMAT_CSR: return launch_csr(p, x, y);
         case SPMV_FORMAT_ELL: return launch_ell(p, x, y);
         case SPMV_FORMAT_HYB:
+        case SPMV_FORMAT_JDS:
             SPMV_RETURN_IF(launch_ell(p, x, y));
             phase_mark(p);  // ell | overflow
             return launch_hyb_overflow(p, x, y);
@@ -336,10 +337,6 @@ static int dispatch(const spmv_plan_s *p, const double *x, double *y) {
         case SPMV_FORMAT_DIA: return launch_dia(p, x, y);
         case SPMV_FORMAT_CSS: return launch_css(p, x, y);
         case SPMV_FORMAT_COO: return launch_coo(p, x, y);
-        case SPMV_FORMAT_JDS:
-            SPMV_RETURN_IF(launch_ell(p, x, y));
-            phase_mark(p);  // ell | overflow
-            return launch_hyb_overflow(p, x, y);
         case SPMV_FORMAT_BIN: return launch_bin(p, x, y);
     }
     set_error("plan has an unknown format");
@@ -351,6 +348,27 @@ static int bind_device(const spmv_plan_s *p) {
     SPMV_HIP_TRY(hipGetDevice(&cur));
     if (cur != p->device) SPMV_HIP_TRY(hipSetDevice(p->device));
     return SPMV_SUCCESS;
+}
+
+// Times `iters` repetitions of `run` (a status; the first failure ends the
+// loop) between two events on `s`.  Both events are destroyed on every path.
+template <class Run>
+static int time_on_stream(hipStream_t s, int32_t iters, double *ms, Run run) {
+    hipEvent_t a = nullptr, b = nullptr;
+    hipError_t e = hipEventCreate(&a);
+    if (e == hipSuccess) e = hipEventCreate(&b);
+    if (e == hipSuccess) e = hipEventRecord(a, s);
+    int st = SPMV_SUCCESS;
+    for (int32_t i = 0; i < iters && st == SPMV_SUCCESS && e == hipSuccess; ++i) st = run();
+    if (e == hipSuccess) e = hipEventRecord(b, s);
+    if (e == hipSuccess) e = hipEventSynchronize(b);
+    float f = 0;
+    if (e == hipSuccess) e = hipEventElapsedTime(&f, a, b);
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+    SPMV_HIP_TRY(e);
+    *ms = f;
+    return st;
 }
 
 }  // namespace spmv
@@ -523,22 +541,7 @@ int spmv_fetch_y(spmv_plan_t p, double *y) {
 int spmv_time(spmv_plan_t p, const double *x_dev, double *y_dev, int32_t iters, double *ms) {
     SPMV_CHECK_ARG(p != nullptr && ms != nullptr && iters > 0, "bad arguments");
     SPMV_RETURN_IF(bind_device(p));
-    // both events are destroyed on every path
-    hipEvent_t a = nullptr, b = nullptr;
-    hipError_t e = hipEventCreate(&a);
-    if (e == hipSuccess) e = hipEventCreate(&b);
-    if (e == hipSuccess) e = hipEventRecord(a, p->stream);
-    int st = SPMV_SUCCESS;
-    for (int i = 0; i < iters && st == SPMV_SUCCESS && e == hipSuccess; ++i) st = dispatch(p, x_dev, y_dev);
-    if (e == hipSuccess) e = hipEventRecord(b, p->stream);
-    if (e == hipSuccess) e = hipEventSynchronize(b);
-    float f = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&f, a, b);
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-    SPMV_HIP_TRY(e);
-    *ms = f;
-    return st;
+    return time_on_stream(p->stream, iters, ms, [&] { return dispatch(p, x_dev, y_dev); });
 }
 
 }  // extern "C"
@@ -546,8 +549,8 @@ int spmv_time(spmv_plan_t p, const double *x_dev, double *y_dev, int32_t iters, 
 // ---- multi-vector execute (Y = A X, k interleaved right-hand sides) ---------
 namespace spmv {
 
-// Widths with a fused kernel, per format, widest first.  Every width of
-// k_multi.hip that beat K single-vector executes on the same plan is listed
+// Widths with a fused kernel (k_dia.hip, k_ell.hip), per format, widest first.
+// Every width that beat K single-vector executes on the same plan is listed
 // (DESIGN §3.7); a width that is not listed is cut narrower.
 static const int kMultiWidthsDia[] = {8, 4, 2};
 static const int kMultiWidthsEll[] = {8, 4, 2};
@@ -721,23 +724,7 @@ int spmv_time_multi(spmv_plan_t p, int32_t k, const double *X_dev, int64_t ldx, 
     SPMV_CHECK_ARG((X_dev != nullptr || p->n == 0) && (Y_dev != nullptr || p->m == 0), "multi execute: X or Y is NULL");
     SPMV_RETURN_IF(bind_device(p));
     p->y_staged = false;
-    // both events are destroyed on every path
-    hipEvent_t a = nullptr, b = nullptr;
-    hipError_t e = hipEventCreate(&a);
-    if (e == hipSuccess) e = hipEventCreate(&b);
-    if (e == hipSuccess) e = hipEventRecord(a, p->stream);
-    int st = SPMV_SUCCESS;
-    for (int i = 0; i < iters && st == SPMV_SUCCESS && e == hipSuccess; ++i)
-        st = multi_dispatch(p, k, X_dev, ldx, Y_dev, ldy);
-    if (e == hipSuccess) e = hipEventRecord(b, p->stream);
-    if (e == hipSuccess) e = hipEventSynchronize(b);
-    float f = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&f, a, b);
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-    SPMV_HIP_TRY(e);
-    *ms = f;
-    return st;
+    return time_on_stream(p->stream, iters, ms, [&] { return multi_dispatch(p, k, X_dev, ldx, Y_dev, ldy); });
 }
 
 }  // extern "C"
@@ -838,20 +825,10 @@ int spmv_graph_time(spmv_graph_t G, int32_t launches, double *ms) {
     SPMV_CHECK_ARG(G != nullptr && G->exec != nullptr && ms != nullptr && launches > 0, "bad arguments");
     SPMV_RETURN_IF(bind_device(G->plan));
     const hipStream_t s = G->plan->stream;
-    hipEvent_t a, b;
-    SPMV_HIP_TRY(hipEventCreate(&a));
-    SPMV_HIP_TRY(hipEventCreate(&b));
-    hipError_t e = hipEventRecord(a, s);
-    for (int32_t i = 0; i < launches && e == hipSuccess; ++i) e = hipGraphLaunch(G->exec, s);
-    if (e == hipSuccess) e = hipEventRecord(b, s);
-    if (e == hipSuccess) e = hipEventSynchronize(b);
-    float f = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&f, a, b);
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-    SPMV_HIP_TRY(e);
-    *ms = f;
-    return SPMV_SUCCESS;
+    return time_on_stream(s, launches, ms, [&]() -> int {
+        SPMV_HIP_TRY(hipGraphLaunch(G->exec, s));
+        return SPMV_SUCCESS;
+    });
 }
 
 int spmv_graph_destroy(spmv_graph_t G) {

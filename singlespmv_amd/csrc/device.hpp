@@ -32,6 +32,37 @@ __device__ __forceinline__ int32_t ld_stream(const int32_t *p) {
 // x gathers: plain cached loads (x is the re-used operand).
 __device__ __forceinline__ double ld_x(const double *x, int32_t c) { return x[c]; }
 
+// A row's K contiguous values (x_j, y_j of K interleaved right-hand sides) as
+// K/2 16-byte loads / nontemporal stores -- the row is 16-byte aligned; K = 1
+// is the single vector: a scalar cached load, a scalar nontemporal store.
+template <int K>
+__device__ __forceinline__ void ld_row(const double *p, double (&g)[K]) {
+    if constexpr (K == 1) {
+        g[0] = p[0];
+    } else {
+#pragma unroll
+        for (int j = 0; j < K; j += 2) {
+            const f64x2 t = *reinterpret_cast<const f64x2 *>(p + j);
+            g[j] = t.x;
+            g[j + 1] = t.y;
+        }
+    }
+}
+template <int K>
+__device__ __forceinline__ void st_row(double *p, const double (&a)[K]) {  // y is not re-read: streamed out
+    if constexpr (K == 1) {
+        __builtin_nontemporal_store(a[0], p);
+    } else {
+#pragma unroll
+        for (int j = 0; j < K; j += 2) {
+            f64x2 t;
+            t.x = a[j];
+            t.y = a[j + 1];
+            __builtin_nontemporal_store(t, reinterpret_cast<f64x2 *>(p + j));
+        }
+    }
+}
+
 // y = a*b + c as a rounded multiply followed by a rounded add.  Keeps the
 // per-row arithmetic identical to the reference's `tmp += val*x`
 // (src/opt_crs.cpp:62-66) as compiled without contraction, so sequential-order

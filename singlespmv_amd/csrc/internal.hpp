@@ -616,9 +616,10 @@ int launch_css(const spmv_plan_s *p, const double *x, double *y);
 int launch_coo(const spmv_plan_s *p, const double *x, double *y);
 int launch_bin(const spmv_plan_s *p, const double *x, double *y);
 int bin_time_mul(const spmv_plan_s *p, const double *x, float *ms);  // one timed Mul pass (build-time)
-// k_multi.hip -- K interleaved right-hand sides (x_j[i] = X[i*ldx + j]): the fused
-// DIA / sliced-ELL kernels (K = 2, 4, 8; X, Y 16-byte aligned, ldx, ldy even)
-// and the strided copies / zero fill of the generic path
+// K interleaved right-hand sides (x_j[i] = X[i*ldx + j]): the fused DIA /
+// sliced-ELL kernels of k_dia.hip / k_ell.hip (K = 2, 4, 8; X, Y 16-byte
+// aligned, ldx, ldy even) and, in k_multi.hip, the strided copies / zero fill
+// of the generic path
 int launch_dia_multi(const spmv_plan_s *p, int K, const double *X, int64_t ldx, double *Y, int64_t ldy);
 int launch_ell_multi(const spmv_plan_s *p, int K, const double *X, int64_t ldx, double *Y, int64_t ldy);
 int launch_multi_copy(const spmv_plan_s *p, int64_t len, const double *src, int64_t src_ld, double *dst,

@@ -17,8 +17,18 @@
 // O32 (x below 4 GB, a slice below 2 GB): the wave's slice base is
 // wave-uniform (SGPR) and every load addresses it, or x, plus a 32-bit byte
 // offset (the global_load saddr form), instead of 64-bit per-lane addresses.
+//
+// K right-hand sides (spmv_execute_multi, K = 2, 4, 8: x_j[i] = X[i*ldx + j],
+// y_j[r] = Y[r*ldy + j], rows 16-byte aligned) run the same body with K
+// accumulators per row, so the slots are streamed once for K vectors: each
+// gathered column c fetches the K contiguous doubles of X row c (K/2 16-byte
+// loads from one or two lines the single-vector gather pulls anyway).  Every
+// column is summed exactly as the single vector is -- column j of Y is bit
+// for bit what spmv_execute gives for column j of X.
 #include "device.hpp"
 #include "internal.hpp"
+
+#include <type_traits>
 
 namespace spmv {
 
@@ -28,14 +38,13 @@ __device__ __forceinline__ const char *ell_at(const void *base, int64_t byte_off
     else return (const char *)base + byte_off;
 }
 
-template <int UNROLL, bool ADD, bool PERM, bool O32 = false>
-__global__ __launch_bounds__(256) void ell_slice_kernel(int64_t m, int64_t n_slices,
-                                                        const int32_t *__restrict__ perm,
-                                                        const int64_t *__restrict__ slice_off,
-                                                        const int32_t *__restrict__ col,
-                                                        const double *__restrict__ val,
-                                                        const double *__restrict__ x,
-                                                        double *__restrict__ y) {
+// UNROLL quads per iteration: 4 UNROLL K doubles of gathers in flight per lane
+template <int K, int UNROLL, bool PERM, bool O32>
+__device__ __forceinline__ void ell_slice_body(int64_t m, int64_t n_slices, const int32_t *__restrict__ perm,
+                                               const int64_t *__restrict__ slice_off,
+                                               const int32_t *__restrict__ col, const double *__restrict__ val,
+                                               const double *__restrict__ X, int64_t ldx, double *__restrict__ Y,
+                                               int64_t ldy) {
     const int64_t slice = (int64_t)blockIdx.x * (blockDim.x / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (slice >= n_slices) return;
@@ -51,11 +60,18 @@ __global__ __launch_bounds__(256) void ell_slice_kernel(int64_t m, int64_t n_sli
     auto ldv = [&](int64_t q, int h) {
         return ld_stream2((const double *)ell_at<O32>(vs, (q * 256 + h * 128 + lane * 2) * 8));
     };
-    auto ldx = [&](int c) -> double {
-        if constexpr (O32) return *(const double *)((const char *)x + (uint32_t)c * 8u);
-        else return ld_x(x, c);
+    const uint32_t ldx8 = O32 ? (uint32_t)ldx * 8u : 0u;
+    auto ldxr = [&](int c, double (&g)[K]) {  // x gathers: plain cached loads (x is the re-used operand)
+        if constexpr (O32) ld_row<K>((const double *)((const char *)X + (uint32_t)c * ldx8), g);
+        else ld_row<K>(X + (int64_t)c * ldx, g);
     };
-    double acc = 0.0;
+    double acc[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc[j] = 0.0;
+    auto add = [&](double v, const double (&g)[K]) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) acc[j] = madd(v, g[j], acc[j]);
+    };
     int64_t q = 0;
     for (; q + UNROLL <= quads; q += UNROLL) {
         i32x4 c[UNROLL];
@@ -66,84 +82,139 @@ __global__ __launch_bounds__(256) void ell_slice_kernel(int64_t m, int64_t n_sli
             a[u] = ldv(q + u, 0);
             b[u] = ldv(q + u, 1);
         }
-        double g[UNROLL][4];
+        double g[UNROLL][4][K];
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u) {
-            g[u][0] = ldx(c[u].x);
-            g[u][1] = ldx(c[u].y);
-            g[u][2] = ldx(c[u].z);
-            g[u][3] = ldx(c[u].w);
+            ldxr(c[u].x, g[u][0]);
+            ldxr(c[u].y, g[u][1]);
+            ldxr(c[u].z, g[u][2]);
+            ldxr(c[u].w, g[u][3]);
         }
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u) {
-            acc = madd(a[u].x, g[u][0], acc);
-            acc = madd(a[u].y, g[u][1], acc);
-            acc = madd(b[u].x, g[u][2], acc);
-            acc = madd(b[u].y, g[u][3], acc);
+            add(a[u].x, g[u][0]);
+            add(a[u].y, g[u][1]);
+            add(b[u].x, g[u][2]);
+            add(b[u].y, g[u][3]);
         }
     }
     for (; q < quads; ++q) {
         const i32x4 c = ldc(q);
         const f64x2 a = ldv(q, 0);
         const f64x2 b = ldv(q, 1);
-        const double g0 = ldx(c.x), g1 = ldx(c.y), g2 = ldx(c.z), g3 = ldx(c.w);
-        acc = madd(a.x, g0, acc);
-        acc = madd(a.y, g1, acc);
-        acc = madd(b.x, g2, acc);
-        acc = madd(b.y, g3, acc);
+        double g[4][K];
+        ldxr(c.x, g[0]);
+        ldxr(c.y, g[1]);
+        ldxr(c.z, g[2]);
+        ldxr(c.w, g[3]);
+        add(a.x, g[0]);
+        add(a.y, g[1]);
+        add(b.x, g[2]);
+        add(b.y, g[3]);
     }
-    if (srow < m) {
-        if (ADD) y[row] = __dadd_rn(y[row], acc);
-        else __builtin_nontemporal_store(acc, y + row);  // not re-read: streamed out
-    }
+    if (srow < m) st_row<K>(Y + row * ldy, acc);
 }
 
-template <int U, bool O32>
-static void launch_ell_uo(const spmv_plan_s *p, const double *x, double *y, size_t lds) {
-    const EllDev &e = p->ell;
-    const int64_t blocks = (e.n_slices + 3) / 4;
-    if (e.perm)
-        hipLaunchKernelGGL((ell_slice_kernel<U, false, true, O32>), dim3((unsigned)blocks), dim3(256), lds,
-                           p->stream, p->m, e.n_slices, e.perm, e.slice_off, e.col, e.val, x, y);
-    else
-        hipLaunchKernelGGL((ell_slice_kernel<U, false, false, O32>), dim3((unsigned)blocks), dim3(256), lds,
-                           p->stream, p->m, e.n_slices, e.perm, e.slice_off, e.col, e.val, x, y);
+// the single vector: K = 1, the unit strides fold away
+template <int UNROLL, bool PERM, bool O32 = false>
+__global__ __launch_bounds__(256) void ell_slice_kernel(int64_t m, int64_t n_slices,
+                                                        const int32_t *__restrict__ perm,
+                                                        const int64_t *__restrict__ slice_off,
+                                                        const int32_t *__restrict__ col,
+                                                        const double *__restrict__ val,
+                                                        const double *__restrict__ x,
+                                                        double *__restrict__ y) {
+    ell_slice_body<1, UNROLL, PERM, O32>(m, n_slices, perm, slice_off, col, val, x, 1, y, 1);
 }
 
-template <int U>
-static void launch_ell_u(const spmv_plan_s *p, const double *x, double *y, size_t lds) {
-    // 32-bit offsets: x below 4 GB and a slice's values below 2 GB
-    bool o32 = p->n < ((int64_t)1 << 29) && (int64_t)p->ell.max_width * 64 * 8 < ((int64_t)1 << 31);
-    if (const char *v = probe_env("SPMV_LAUNCH_ELL_O32")) o32 = o32 && std::atoi(v) != 0;
-    if (o32) launch_ell_uo<U, true>(p, x, y, lds);
-    else launch_ell_uo<U, false>(p, x, y, lds);
+template <int K, int UNROLL, bool PERM, bool O32>
+__global__ __launch_bounds__(256) void ell_slice_multi_kernel(int64_t m, int64_t n_slices,
+                                                              const int32_t *__restrict__ perm,
+                                                              const int64_t *__restrict__ slice_off,
+                                                              const int32_t *__restrict__ col,
+                                                              const double *__restrict__ val,
+                                                              const double *__restrict__ X, int64_t ldx,
+                                                              double *__restrict__ Y, int64_t ldy) {
+    ell_slice_body<K, UNROLL, PERM, O32>(m, n_slices, perm, slice_off, col, val, X, ldx, Y, ldy);
 }
 
 constexpr int kEllLdsKb = 64;  // LDS per workgroup of a large ELL launch: 2 workgroups per CU
 
+// Above 256 MB of slots the launch requests 64 KB of LDS: two workgroups
+// (8 waves, ~48 KB of slots in flight) per CU instead of the 8 the
+// registers allow -- fewer concurrent streams, as DIA's cap (config 4,
+// same plans: 2.421-2.425 -> 2.382-2.387 ms over three plans,
+// profiles/round4/probe/c4_ell_window_variants.jsonl).
+static size_t ell_lds(const EllDev &e) {
+    return (size_t)e.slots * sizeof(double) >= kStreamVmmMinBytes ? (size_t)kEllLdsKb * 1024 : 0;
+}
+
+// 32-bit byte offsets: the X block below 4 GB and a slice's values below 2 GB
+static bool ell_o32(const spmv_plan_s *p, int64_t ldx) {
+    return p->n * ldx < ((int64_t)1 << 29) && ldx < ((int64_t)1 << 28) &&
+           (int64_t)p->ell.max_width * 64 * 8 < ((int64_t)1 << 31);
+}
+
+// one launch of K vectors, U quads per iteration (K = 1: ldx = ldy = 1)
+template <int K, int U>
+static void launch_ell_ku(const spmv_plan_s *p, const double *X, int64_t ldx, double *Y, int64_t ldy, size_t lds,
+                          bool o32) {
+    const EllDev &e = p->ell;
+    const dim3 blocks((unsigned)((e.n_slices + 3) / 4));
+    auto go = [&](auto perm, auto o) {
+        constexpr bool P = decltype(perm)::value, O = decltype(o)::value;
+        if constexpr (K == 1)
+            hipLaunchKernelGGL((ell_slice_kernel<U, P, O>), blocks, dim3(256), lds, p->stream, p->m, e.n_slices,
+                               e.perm, e.slice_off, e.col, e.val, X, Y);
+        else
+            hipLaunchKernelGGL((ell_slice_multi_kernel<K, U, P, O>), blocks, dim3(256), lds, p->stream, p->m,
+                               e.n_slices, e.perm, e.slice_off, e.col, e.val, X, ldx, Y, ldy);
+    };
+    auto go_o = [&](auto perm) {
+        if (o32) go(perm, std::true_type{});
+        else go(perm, std::false_type{});
+    };
+    if (e.perm) go_o(std::true_type{});
+    else go_o(std::false_type{});
+}
+
 int launch_ell(const spmv_plan_s *p, const double *x, double *y) {
     const EllDev &e = p->ell;
     if (e.n_slices == 0) return SPMV_SUCCESS;
-    // Above 256 MB of slots the launch requests 64 KB of LDS: two workgroups
-    // (8 waves, ~48 KB of slots in flight) per CU instead of the 8 the
-    // registers allow -- fewer concurrent streams, as DIA's cap (config 4,
-    // same plans: 2.421-2.425 -> 2.382-2.387 ms over three plans,
-    // profiles/round4/probe/c4_ell_window_variants.jsonl).
     // The product runs 2 quads (4 slots each) per lane per iteration; the
     // probe build adds launch-time unroll 1 / 4 and LDS-request variants.
-    size_t lds = (size_t)e.slots * sizeof(double) >= kStreamVmmMinBytes ? kEllLdsKb * 1024 : 0;
+    size_t lds = ell_lds(e);
+    bool o32 = ell_o32(p, 1);
+    if (const char *v = probe_env("SPMV_LAUNCH_ELL_O32")) o32 = o32 && std::atoi(v) != 0;
 #ifdef SPMV_PROBES
     int unroll = e.unroll;
     if (const char *v = probe_env("SPMV_LAUNCH_ELL_UNROLL")) unroll = std::atoi(v);
     if (const char *v = probe_env("SPMV_LAUNCH_ELL_LDS_KB")) lds = (size_t)std::atoi(v) * 1024;
     switch (unroll) {
-        case 1: launch_ell_u<1>(p, x, y, lds); break;
-        case 4: launch_ell_u<4>(p, x, y, lds); break;
-        default: launch_ell_u<2>(p, x, y, lds);
+        case 1: launch_ell_ku<1, 1>(p, x, 1, y, 1, lds, o32); break;
+        case 4: launch_ell_ku<1, 4>(p, x, 1, y, 1, lds, o32); break;
+        default: launch_ell_ku<1, 2>(p, x, 1, y, 1, lds, o32);
     }
 #else
-    launch_ell_u<2>(p, x, y, lds);
+    launch_ell_ku<1, 2>(p, x, 1, y, 1, lds, o32);
 #endif
+    SPMV_HIP_TRY(hipGetLastError());
+    return SPMV_SUCCESS;
+}
+
+// 2, 2, 1 quads per iteration for K = 2, 4, 8 (65 / 95 / 97 VGPRs as
+// compiled with O32, 78 / 106 / 100 without; no scratch: K = 8 at 2 quads would
+// hold 128 VGPRs of gathers alone)
+int launch_ell_multi(const spmv_plan_s *p, int K, const double *X, int64_t ldx, double *Y, int64_t ldy) {
+    if (p->ell.n_slices == 0) return SPMV_SUCCESS;
+    const size_t lds = ell_lds(p->ell);
+    const bool o32 = ell_o32(p, ldx);
+    switch (K) {
+        case 2: launch_ell_ku<2, 2>(p, X, ldx, Y, ldy, lds, o32); break;
+        case 4: launch_ell_ku<4, 2>(p, X, ldx, Y, ldy, lds, o32); break;
+        case 8: launch_ell_ku<8, 1>(p, X, ldx, Y, ldy, lds, o32); break;
+        default: set_error("ell multi: no kernel of this width"); return SPMV_ERROR_INVALID_VALUE;
+    }
     SPMV_HIP_TRY(hipGetLastError());
     return SPMV_SUCCESS;
 }

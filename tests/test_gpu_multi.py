@@ -15,6 +15,7 @@ Needs an MI355X: `pytest -m gpu`.
 import numpy as np
 import pytest
 
+import guarded_buffers as gb
 import multi_inputs as mi
 import signed_inputs as si
 import singlespmv_amd as sp
@@ -98,6 +99,31 @@ def test_dia_window_limits(name, k):
     info = plan.info()
     assert info["format"] == "dia" and info["n_diags"] == 3
     _multi(plan, name, "cancel", k, mi.ld_for(k), f"dia-{name}", fused=None)
+    plan.destroy()
+
+
+@pytest.mark.parametrize("y_off", [0, 1])
+@pytest.mark.parametrize("name", sorted(mi.TRIDIAGS))
+def test_dia_single_store_branches(name, y_off):
+    """The single-vector DIA kernel with its x window in LDS (tri1500, 3 513
+    doubles) and with x from global memory (tri5000, 10 513 > 8 192), each
+    storing the row pair as one 16-byte word (y_off 0) and as two scalars
+    (y_off 1: y 8 bytes past a 16-byte boundary).  12 001 rows: the last lane
+    holds one row.  Bit for bit against the oracle, guards untouched."""
+    import torch
+    c = mi.case(name, "cancel")
+    m = c["m"]
+    plan = _plan(c, "dia")
+    assert plan.info()["format"] == "dia" and plan.info()["n_diags"] == 3
+    x = torch.from_numpy(np.array(c["x"])).cuda()
+    ybuf, y = gb.guarded_device(m, y_off, gb.Y_FILL)
+    assert y.data_ptr() % 16 == 8 * y_off
+    plan.execute(x, y)
+    torch.cuda.synchronize()
+    got = gb.used(ybuf, m, y_off)
+    assert not gb.guard_damage(ybuf, m, y_off, gb.Y_FILL), f"dia-{name} y+{y_off}: a y guard was written"
+    assert mi.bits(got)[m - 1] != mi.bits(np.array([gb.Y_FILL]))[0], f"dia-{name} y+{y_off}: last row not written"
+    assert np.array_equal(mi.bits(got), mi.bits(c["y_oracle"])), f"dia-{name} y+{y_off}: differs from the oracle"
     plan.destroy()
 
 

@@ -5,10 +5,10 @@ The kernels form the byte offset of x[c] in 32 bits while x stays below 4 GiB
 and in 64 bits beyond.  The switch sits at n = 2^29 (WIDE) in
 
     formats.cpp  csr_plan_lanes     c.off32 = slab_max + 512 < 2^28 && p->n < 2^29
-    k_ell.hip    launch_ell_u       o32 = p->n < 2^29 && max_width * 64 * 8 < 2^31
-    k_multi.hip  launch_ell_multi_k o32 = p->n * ldx < 2^29 && ldx < 2^28 && ...
+    k_ell.hip    ell_o32(p, ldx)    p->n * ldx < 2^29 && ldx < 2^28 && max_width * 64 * 8 < 2^31
 
-(the last one at n = 2^26 for ldx = 8, MULTI_WIDE).  A wrong offset does not
+(ldx = 1 for the single vector; the fused multi-vector launch reaches it at
+n = 2^26 for ldx = 8, MULTI_WIDE).  A wrong offset does not
 fault: it reads x[c mod 2^29] and returns a finite, plausible y.  Only x has to
 be big to get there, so the matrices here have about 4 000 rows and at most
 about 150 k entries.
