@@ -196,17 +196,37 @@ static int csr_bin_of(int64_t len) {
     return b;
 }
 
-// Rows 0..m-1 of a CSR grouped by length bin (ascending within a bin).
-static void csr_bin_rows(const int64_t *row_ptr, int64_t m, std::vector<int32_t> &rows,
-                         int64_t off[kCsrBins + 1]) {
+// Rows 0..m-1 of a CSR grouped by length bin, ascending within a bin: bin b
+// is rows[off[b], off[b + 1]).  Returns the longest row.
+static int64_t csr_bin_rows(const int64_t *row_ptr, int64_t m, std::vector<int32_t> &rows,
+                            int64_t off[kCsrBins + 1]) {
+    std::vector<uint8_t> bin((size_t)std::max<int64_t>(m, 1));
     int64_t cnt[kCsrBins] = {0};
-    for (int64_t r = 0; r < m; ++r) ++cnt[csr_bin_of(row_ptr[r + 1] - row_ptr[r])];
+    int64_t maxlen = 0;
+#pragma omp parallel
+    {
+        int64_t lc[kCsrBins] = {0}, lmax = 0;
+#pragma omp for schedule(static)
+        for (int64_t r = 0; r < m; ++r) {
+            const int64_t len = row_ptr[r + 1] - row_ptr[r];
+            const int b = csr_bin_of(len);
+            bin[(size_t)r] = (uint8_t)b;
+            ++lc[b];
+            lmax = std::max(lmax, len);
+        }
+#pragma omp critical
+        {
+            for (int b = 0; b < kCsrBins; ++b) cnt[b] += lc[b];
+            maxlen = std::max(maxlen, lmax);
+        }
+    }
     off[0] = 0;
     for (int b = 0; b < kCsrBins; ++b) off[b + 1] = off[b] + cnt[b];
     int64_t pos[kCsrBins];
     for (int b = 0; b < kCsrBins; ++b) pos[b] = off[b];
     rows.resize((size_t)m);
-    for (int64_t r = 0; r < m; ++r) rows[(size_t)pos[csr_bin_of(row_ptr[r + 1] - row_ptr[r])]++] = (int32_t)r;
+    for (int64_t r = 0; r < m; ++r) rows[(size_t)pos[bin[(size_t)r]]++] = (int32_t)r;
+    return maxlen;
 }
 
 // Lanes per row.  An explicit csr_lanes applies to every row.  AUTO bins the
@@ -238,47 +258,20 @@ int csr_plan_lanes(spmv_plan_s *p, const int64_t *row_ptr, int64_t m, const spmv
         }
         return SPMV_SUCCESS;
     }
-    auto bin_of = [](int64_t len) {
-        if (len > 4096) return kCsrBins - 1;
-        int b = 0;
-        while (b < kCsrBins - 2 && 4 * (int64_t)kCsrBinLanes[b] < len) ++b;
-        return b;
-    };
-    std::vector<uint8_t> bin((size_t)std::max<int64_t>(m, 1));
-    int64_t cnt[kCsrBins] = {0};
-    int64_t maxlen = 0;
-#pragma omp parallel
-    {
-        int64_t lc[kCsrBins] = {0}, lmax = 0;
-#pragma omp for schedule(static)
-        for (int64_t r = 0; r < m; ++r) {
-            const int64_t len = row_ptr[r + 1] - row_ptr[r];
-            const int b = bin_of(len);
-            bin[(size_t)r] = (uint8_t)b;
-            ++lc[b];
-            lmax = std::max(lmax, len);
-        }
-#pragma omp critical
-        {
-            for (int b = 0; b < kCsrBins; ++b) cnt[b] += lc[b];
-            maxlen = std::max(maxlen, lmax);
-        }
-    }
+    std::vector<int32_t> rows;
+    int64_t off[kCsrBins + 1];
+    const int64_t maxlen = csr_bin_rows(row_ptr, m, rows, off);
+    auto cnt = [&](int b) { return off[b + 1] - off[b]; };
     int d = 0;
     for (int b = 1; b < kCsrBins; ++b)
-        if (cnt[b] > cnt[d]) d = b;
-    if (m == 0 || (d < kCsrBins - 1 && (double)cnt[d] >= 0.99 * (double)m && cnt[kCsrBins - 1] == 0 &&
+        if (cnt(b) > cnt(d)) d = b;
+    if (m == 0 || (d < kCsrBins - 1 && (double)cnt(d) >= 0.99 * (double)m && cnt(kCsrBins - 1) == 0 &&
                    maxlen <= 64 * (int64_t)kCsrBinLanes[d])) {
         c.lanes = m ? kCsrBinLanes[d] : 1;
         return SPMV_SUCCESS;
     }
     c.lanes = 0;
-    c.bin_off[0] = 0;
-    for (int b = 0; b < kCsrBins; ++b) c.bin_off[b + 1] = c.bin_off[b] + cnt[b];
-    std::vector<int32_t> rows((size_t)m);
-    int64_t pos[kCsrBins];
-    for (int b = 0; b < kCsrBins; ++b) pos[b] = c.bin_off[b];
-    for (int64_t r = 0; r < m; ++r) rows[(size_t)pos[bin[(size_t)r]]++] = (int32_t)r;
+    std::copy(off, off + kCsrBins + 1, c.bin_off);
     return plan_upload(p, &c.bin_rows, rows.data(), m);
 }
 
@@ -305,7 +298,7 @@ int csr_windows_finish(spmv_plan_s *p, const std::vector<int32_t> &lo, const std
         }
         c.win_s[si] = span <= kCsrMaxWin ? (int32_t)span : 0;
     }
-    const int sd = kCsrSlabsPerWave == 4 ? 2 : kCsrSlabsPerWave == 2 ? 1 : 0;
+    constexpr int sd = csr_win_index(kCsrSlabsPerWave);
     if (!c.win_s[sd]) return SPMV_SUCCESS;
     c.win = c.win_s[sd];
     std::vector<int32_t> w0(lo);

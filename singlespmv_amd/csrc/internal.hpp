@@ -142,6 +142,8 @@ constexpr int kCsrBinLanes[kCsrBins] = {1, 2, 4, 8, 16, 32, 64, 256};
 constexpr int kCsrMaxWin = 4096;   // columns of a csr_slabx x window (32 KB of LDS)
 constexpr int kCsrWinGroup = 256;  // rows of one x-window granule (4 waves x 1 slab of 64)
 constexpr int kCsrSlabsPerWave = 1;  // csr_slabx default: a workgroup owns 1 granule (256 rows)
+// CsrDev::win_s index of a workgroup of S = 1, 2 or 4 granules
+constexpr int csr_win_index(int S) { return S == 4 ? 2 : S == 1 ? 0 : 1; }
 struct CsrDev {
     void *row_ptr = nullptr;  // int32 or int64 [m+1]
     bool rp64 = false;

@@ -2,19 +2,31 @@
 // (src/opt_crs.cpp:57-69, `y[i] = sum_j val[j] * x[idx[j]]`) re-designed for
 // wave64.
 //
-// The product kernels: csr_slab2 (near-uniform rows, below) and
-// csr_adaptive (rows binned by length).  csr_vec4 is the round-3 kernel whose
-// order of arithmetic both keep; the probe build still launches it for A/Bs
-// (SPMV_LAUNCH_CSR=0).
-//
-// csr_vec4<L, RP>: a group of L lanes (L | 64) owns one row.  The group walks
-// the row from its 16-byte-aligned start a = ptr[i] & ~3 in chunks of 4*L
-// entries; each lane issues ONE 16-byte load of 4 column indices and TWO
-// 16-byte loads of 4 values (non-temporal: streamed once), so a wave
+// One order of arithmetic: a group of L lanes (L | 64, or a workgroup's 256)
+// owns a row and walks it from its 16-byte-aligned start a = ptr[i] & ~3 in
+// chunks of 4 L entries; each lane takes ONE 16-byte load of 4 column indices
+// and TWO 16-byte loads of 4 values (non-temporal: streamed once), so a wave
 // instruction covers 1 KiB contiguous when rows are contiguous.  Entries
-// outside [ptr[i], ptr[i+1]) are masked (no gather).  Each lane sums its
-// entries in order, then the group reduces with a fixed butterfly; lane 0
-// writes y[i] (β = 0, idempotent).
+// outside [ptr[i], ptr[i+1]) never reach the sum.  Each lane sums its entries
+// in order, then the group reduces with a fixed butterfly (β = 0, idempotent).
+//
+// Two shared pieces state that arithmetic:
+//   csr_row_sum<STRIDE>             a lane's walk of one row (any length)
+//   csr_batch_load / csr_batch_sum  one wave, U steps of 64 / L rows each of a
+//                                   64-row slab: the loads of all U steps
+//                                   issued together, no divergence on rows of
+//                                   one chunk
+// and three product kernels use them:
+//   csr_slab2<L>   near-uniform rows: one wave per 64-row slab, x gathered
+//                  from global memory, batch after batch (config 2)
+//   csr_slabx<L>   the same slabs on rows near the diagonal: x from one LDS
+//                  window per workgroup, the col / val stream one batch ahead
+//                  of the sums (config 4)
+//   csr_adaptive   skewed rows binned by length, all bins in one launch, a
+//                  row per L-lane group or per workgroup (config 3; its ADD
+//                  instance finishes the HYB / JDS overflow rows)
+// csr_vec4<L> (a row per group, no slabs: the round-3 kernel) is compiled
+// into the probe build only, for A/Bs (SPMV_LAUNCH_CSR=0).
 //
 // Algorithmic bytes per row: 12*nnz_i + rp bytes + 8 (y) and the
 // x gathers (8*n total, counted once).
@@ -34,6 +46,47 @@ __device__ __forceinline__ I csr_vpos(I j) {  // j % 4 == 0
     return (j & ~(I)255) + ((j & 255) >> 1);
 }
 
+// The lane's in-order partial sum of row [s, e): its 4-entry groups at
+// (s & ~3) + 4 lane + 4 STRIDE i.  Entries outside [s, e) are masked: no x
+// gather, no add.  vh: the values are stored in halves (csr_vpos).
+template <int STRIDE>
+__device__ __forceinline__ double csr_row_sum(int64_t s, int64_t e, int lane, const int32_t *__restrict__ col,
+                                              const double *__restrict__ val, const double *__restrict__ x,
+                                              bool vh) {
+    double acc = 0.0;
+    for (int64_t j = (s & ~(int64_t)3) + 4 * lane; j < e; j += 4 * STRIDE) {
+        const i32x4 c = ld_stream4(col + j);
+        const int64_t vj = vh ? csr_vpos(j) : j;
+        const f64x2 v01 = ld_stream2(val + vj);
+        const f64x2 v23 = ld_stream2(val + vj + (vh ? 128 : 2));
+        const bool in0 = j + 0 >= s && j + 0 < e, in1 = j + 1 >= s && j + 1 < e;
+        const bool in2 = j + 2 >= s && j + 2 < e, in3 = j + 3 >= s && j + 3 < e;
+        // masked gathers: only entries of this row
+        const double x0 = in0 ? ld_x(x, c.x) : 0.0;
+        const double x1 = in1 ? ld_x(x, c.y) : 0.0;
+        const double x2 = in2 ? ld_x(x, c.z) : 0.0;
+        const double x3 = in3 ? ld_x(x, c.w) : 0.0;
+        if (in0) acc = madd(v01.x, x0, acc);
+        if (in1) acc = madd(v01.y, x1, acc);
+        if (in2) acc = madd(v23.x, x2, acc);
+        if (in3) acc = madd(v23.y, x3, acc);
+    }
+    return acc;
+}
+
+// ADD: y[yrow[row]] += sum (the HYB/JDS overflow, one writer per row);
+// otherwise y[row] = sum
+template <bool ADD>
+__device__ __forceinline__ void csr_store_row(double *__restrict__ y, const int32_t *__restrict__ yrow, int64_t row,
+                                              double sum) {
+    if (ADD) {
+        const int64_t yi = yrow[row];
+        y[yi] = __dadd_rn(y[yi], sum);
+    } else {
+        y[row] = sum;
+    }
+}
+
 template <int L, typename RP>
 __global__ __launch_bounds__(256) void csr_vec4_kernel(int64_t m,
                                                        const RP *__restrict__ rp,
@@ -42,161 +95,192 @@ __global__ __launch_bounds__(256) void csr_vec4_kernel(int64_t m,
                                                        const double *__restrict__ x,
                                                        double *__restrict__ y, bool vh) {
     const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t g = gtid / L;
+    const int64_t row = gtid / L;
     const int lane = threadIdx.x & (L - 1);
-    if (g >= m) return;  // whole groups exit together (L | 256)
-    const int64_t row = g;
-    const int64_t s = rp[row];
-    const int64_t e = rp[row + 1];
-    double acc = 0.0;
-    for (int64_t j = (s & ~(int64_t)3) + 4 * lane; j < e; j += 4 * L) {
-        const i32x4 c = ld_stream4(col + j);
-        const int64_t vj = vh ? csr_vpos(j) : j;
-        const f64x2 v01 = ld_stream2(val + vj);
-        const f64x2 v23 = ld_stream2(val + vj + (vh ? 128 : 2));
-        // masked gathers: only entries of this row
-        const double x0 = (j + 0 >= s && j + 0 < e) ? ld_x(x, c.x) : 0.0;
-        const double x1 = (j + 1 >= s && j + 1 < e) ? ld_x(x, c.y) : 0.0;
-        const double x2 = (j + 2 >= s && j + 2 < e) ? ld_x(x, c.z) : 0.0;
-        const double x3 = (j + 3 >= s && j + 3 < e) ? ld_x(x, c.w) : 0.0;
-        if (j + 0 >= s && j + 0 < e) acc = madd(v01.x, x0, acc);
-        if (j + 1 >= s && j + 1 < e) acc = madd(v01.y, x1, acc);
-        if (j + 2 >= s && j + 2 < e) acc = madd(v23.x, x2, acc);
-        if (j + 3 >= s && j + 3 < e) acc = madd(v23.y, x3, acc);
-    }
-    acc = group_sum<L>(acc);
+    if (row >= m) return;  // whole groups exit together (L | 256)
+    const double acc = group_sum<L>(csr_row_sum<L>(rp[row], rp[row + 1], lane, col, val, x, vh));
     if (lane == 0) y[row] = acc;
 }
 
-// csr_slab2<L, U, O32> (the product CSR kernel for near-uniform rows): one
-// wave per slab of 64 consecutive rows, the 64 / L rows of a step summed by
-// L-lane groups exactly as csr_vec4<L> sums them (same chunks, same order,
-// same butterfly: bit-identical y), U steps' col / val loads issued before
-// their gathers.  A long-lived wave replaces 64 / (256 / L) short ones and y
-// leaves in one coalesced store per wave (config 4, same plans: csr_vec4<16>
-// 2.82 -> 2.48 ms, profiles/round4/probe/c4_csr_slab2_first.jsonl).  No divergent control flow on the
-// common path.  Lanes past their row's end load the row's first chunk again (same
-// lines, no new traffic) and every loaded column is a real column (plan
-// creation validated them; the kPad tail is zero), so the col / val loads
-// and the x gathers are unconditional.  When every row of a batch of U steps
-// is one aligned chunk of its group (4L entries from a 16-byte boundary:
-// configs 2 and 4) the adds run unmasked; otherwise an entry outside [s, e)
-// is dropped by a select on its add (one 32-bit compare per entry) -- either
-// way the arithmetic of csr_vec4.  Group sums by DPP (group_sum_dpp:
-// bit-identical to group_sum), the row sums through a 512-B LDS slab per
-// wave, then one coalesced store.  Row pointers are exchanged by ds_bpermute
-// as 32-bit values relative to the slab's first entry.  O32 (CsrDev::off32:
-// every slab's byte span and x's fit 31 / 32 bits): the col / val loads and
-// the x gathers address a wave-uniform base plus a 32-bit byte offset (the
-// global_load saddr form: no 64-bit address arithmetic per lane).
+// ---- the slab batch (csr_slab2, csr_slabx) ---------------------------------
+// A wave owns a slab of 64 consecutive rows and sums it in L steps of R = 64 /
+// L rows, row (st R + g) of the slab by lane group g in step st, exactly as
+// csr_row_sum<L> and group_sum<L> sum it (same chunks, same order, same
+// butterfly: both kernels and csr_vec4<L> give bit-identical y).  A batch is
+// U steps whose col / val loads are issued before their x reads.  A
+// long-lived wave replaces 64 / (256 / L) short ones and y leaves in one
+// coalesced store per slab (config 4, same plans: csr_vec4<16> 2.82 -> 2.48
+// ms, profiles/round4/probe/c4_csr_slab2_first.jsonl).
+
+// O32 (CsrDev::off32: every slab's byte span and x's fit 31 / 32 bits): the
+// col / val loads and the x gathers address a wave-uniform base plus a 32-bit
+// byte offset (the global_load saddr form: no 64-bit address arithmetic per
+// lane).
 template <bool O32>
 __device__ __forceinline__ const void *at_bytes(const void *base, int idx, int size) {
     if constexpr (O32) return (const char *)base + (uint32_t)idx * (uint32_t)size;
     else return (const char *)base + (int64_t)idx * size;
 }
 
+// A wave's col / val stream: entry positions are 32-bit, relative to base =
+// the wave's first entry rounded down to 4 (a slab of 64 rows holds < 2^31
+// entries).
+template <bool O32>
+struct CsrStream {
+    const int32_t *cb;
+    const double *vb;
+    int vo, vstep;
+    bool vh;
+    __device__ __forceinline__ CsrStream(const int32_t *col, const double *val, int64_t base, bool halves)
+        : cb(col + base), vh(halves) {
+        const int64_t vbase = vh ? base & ~(int64_t)255 : base;
+        vb = val + vbase;
+        vo = (int)(base - vbase);
+        vstep = vh ? 128 : 2;
+    }
+    // the aligned 4-entry group at j: 4 columns, values 0-1 and 2-3
+    __device__ __forceinline__ void load(int j, i32x4 &c, f64x2 &v01, f64x2 &v23) const {
+        c = ld_stream4((const int32_t *)at_bytes<O32>(cb, j, 4));
+        const int vj = vh ? csr_vpos(j + vo) : j;
+        v01 = ld_stream2((const double *)at_bytes<O32>(vb, vj, 8));
+        v23 = ld_stream2((const double *)at_bytes<O32>(vb, vj + vstep, 8));
+    }
+};
+
+template <int L, int U>
+struct CsrBatch {
+    i32x4 c[U];
+    f64x2 a[U], b[U];
+    int s[U], len[U];  // the row's start (relative to the stream's base) and length
+    bool full;         // every row of the lane is one aligned chunk of its group
+};
+
+// Issue the loads of steps st .. st + U - 1.  rpl: lane t holds the start of
+// the slab's row t, rpe: the slab's end; the row starts are exchanged by
+// ds_bpermute.  Lanes past their row's end load the row's first chunk again
+// (same lines, no new traffic) and every loaded column is a real column (plan
+// creation validated them; the kPad tail is zero), so the loads and the x
+// reads that follow are unconditional.
+template <int L, int U, bool O32>
+__device__ __forceinline__ void csr_batch_load(CsrBatch<L, U> &B, const CsrStream<O32> &A, int rpl, int rpe, int st) {
+    constexpr int R = 64 / L;
+    const int lane = threadIdx.x & 63, g = lane / L, gl = lane & (L - 1);
+    B.full = true;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int li = (st + u) * R + g;
+        const int s = __shfl(rpl, li, 64);
+        const int nx = __shfl(rpl, (li + 1) & 63, 64);
+        const int e = li == 63 ? rpe : nx;
+        const int a0 = s & ~3;
+        B.s[u] = s;
+        B.len[u] = e - s;
+        B.full = B.full && (s & 3) == 0 && B.len[u] == 4 * L;
+        const int j0 = a0 + 4 * gl;
+        A.load(j0 < e ? j0 : a0, B.c[u], B.a[u], B.b[u]);
+    }
+}
+
+// Read the batch's x through xr(column) and write its U R row sums to ys (the
+// wave's 64 sums in LDS).  A lane's four products of a step are formed first
+// (madd's rounded multiply) and then added in entry order, so both add paths
+// start from the same values.  When every row of the batch is one aligned chunk
+// of its group (4 L entries from a 16-byte boundary: configs 2 and 4) the
+// adds run unmasked; otherwise an entry outside [s, e) is dropped by a select
+// on its add (one 32-bit compare per entry), and a row longer than one chunk
+// takes the rest in order.  Group sums by DPP (group_sum_dpp: bit-identical
+// to group_sum).
+template <int L, int U, bool O32, typename XR>
+__device__ __forceinline__ void csr_batch_sum(const CsrBatch<L, U> &B, const CsrStream<O32> &A, const XR &xr,
+                                              double *ys, int st) {
+    constexpr int R = 64 / L;
+    const int lane = threadIdx.x & 63, g = lane / L, gl = lane & (L - 1);
+    double pr[U][4];  // the lane's products, in entry order
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        pr[u][0] = __dmul_rn(B.a[u].x, xr(B.c[u].x));
+        pr[u][1] = __dmul_rn(B.a[u].y, xr(B.c[u].y));
+        pr[u][2] = __dmul_rn(B.b[u].x, xr(B.c[u].z));
+        pr[u][3] = __dmul_rn(B.b[u].y, xr(B.c[u].w));
+    }
+    auto row_done = [&](int u, double acc) {
+        acc = group_sum_dpp<L>(acc);
+        if (gl == 0) ys[(st + u) * R + g] = acc;
+    };
+    if (__ballot(!B.full) == 0) {  // no lane with a partial row: unmasked adds
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            double acc = 0.0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc = __dadd_rn(acc, pr[u][q]);
+            row_done(u, acc);
+        }
+        return;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        // the lane's first group: at j0, rel entries past the row's start
+        const int j0 = (B.s[u] & ~3) + 4 * gl;
+        const int rel = j0 - B.s[u];
+        const int e = B.s[u] + B.len[u];  // the row's end
+        double acc = 0.0, t;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            t = __dadd_rn(acc, pr[u][q]);
+            acc = (unsigned)(rel + q) < (unsigned)B.len[u] ? t : acc;
+        }
+        // rows longer than one chunk of the group: the rest in order
+        for (int jj = j0 + 4 * L; jj < e; jj += 4 * L) {
+            i32x4 cc;
+            f64x2 v01, v23;
+            A.load(jj, cc, v01, v23);
+            const double x0 = xr(cc.x), x1 = xr(cc.y), x2 = xr(cc.z), x3 = xr(cc.w);
+            acc = madd(v01.x, x0, acc);
+            t = madd(v01.y, x1, acc);
+            acc = jj + 1 < e ? t : acc;
+            t = madd(v23.x, x2, acc);
+            acc = jj + 2 < e ? t : acc;
+            t = madd(v23.y, x3, acc);
+            acc = jj + 3 < e ? t : acc;
+        }
+        row_done(u, acc);
+    }
+}
+
+// the wave's 64 row sums, written by its group leaders, leave LDS in one
+// coalesced store
+__device__ __forceinline__ void csr_slab_store(const double *ys, double *__restrict__ y, int64_t r0, int64_t m) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int lane = threadIdx.x & 63;
+    if (r0 + lane < m) __builtin_nontemporal_store(ys[lane], y + r0 + lane);
+}
+
+// csr_slab2<L, U, O32>: one wave per slab; each batch is loaded, gathered
+// from x in global memory and summed before the next one.
 template <int L, typename RP, int U, bool O32>
 __global__ __launch_bounds__(256) void csr_slab2_kernel(int64_t m, const RP *__restrict__ rp,
                                                         const int32_t *__restrict__ col,
                                                         const double *__restrict__ val,
                                                         const double *__restrict__ x, double *__restrict__ y, bool vh) {
-    constexpr int R = 64 / L;  // rows per step
     __shared__ double ysl[4][64];
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform (SGPR)
     const int lane = threadIdx.x & 63;
     const int64_t r0 = ((int64_t)blockIdx.x * 4 + wv) * 64;
     if (r0 >= m) return;  // wave-uniform
-    const int g = lane / L, gl = lane & (L - 1);
     const int64_t rl = r0 + lane;
-    auto ldx = [&](int c) -> double { return *(const double *)at_bytes<O32>(x, c, 8); };
-    // the slab's entries [base, end) (a slab of 64 rows holds < 2^31 entries:
-    // its offsets are 32-bit)
     const int64_t base = (int64_t)rp[r0] & ~(int64_t)3;
     const int rpl = (int)((int64_t)rp[rl < m ? rl : m] - base);            // lane t: row r0 + t's start
     const int rpe = (int)((int64_t)rp[r0 + 64 < m ? r0 + 64 : m] - base);  // the slab's end
-    const int32_t *cb = col + base;
-    const int64_t vbase = vh ? base & ~(int64_t)255 : base;
-    const double *vb = val + vbase;
-    const int vo = (int)(base - vbase), vstep = vh ? 128 : 2;
-    auto vpos = [&](int j) -> int { return vh ? csr_vpos(j + vo) : j; };
+    const CsrStream<O32> A(col, val, base, vh);
+    auto xg = [&](int c) -> double { return *(const double *)at_bytes<O32>(x, c, 8); };
     for (int st = 0; st < L; st += U) {
-        int j0[U], rel[U], len[U];
-        bool full = true;
-        i32x4 c[U];
-        f64x2 a[U], b[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int li = (st + u) * R + g;
-            const int s = __shfl(rpl, li, 64);
-            const int nx = __shfl(rpl, (li + 1) & 63, 64);
-            const int e = li == 63 ? rpe : nx;
-            const int a0 = s & ~3;
-            j0[u] = a0 + 4 * gl;
-            rel[u] = j0[u] - s;
-            len[u] = e - s;
-            full = full && (s & 3) == 0 && len[u] == 4 * L;
-            const int jl = j0[u] < e ? j0[u] : a0;
-            c[u] = ld_stream4((const int32_t *)at_bytes<O32>(cb, jl, 4));
-            const int vj = vpos(jl);
-            a[u] = ld_stream2((const double *)at_bytes<O32>(vb, vj, 8));
-            b[u] = ld_stream2((const double *)at_bytes<O32>(vb, vj + vstep, 8));
-        }
-        double gx[U][4];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            gx[u][0] = ldx(c[u].x);
-            gx[u][1] = ldx(c[u].y);
-            gx[u][2] = ldx(c[u].z);
-            gx[u][3] = ldx(c[u].w);
-        }
-        if (__ballot(!full) == 0) {  // no lane with a partial row: unmasked adds
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                double acc = 0.0;
-                acc = madd(a[u].x, gx[u][0], acc);
-                acc = madd(a[u].y, gx[u][1], acc);
-                acc = madd(b[u].x, gx[u][2], acc);
-                acc = madd(b[u].y, gx[u][3], acc);
-                acc = group_sum_dpp<L>(acc);
-                if (gl == 0) ysl[wv][(st + u) * R + g] = acc;
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                double acc = 0.0, t;
-                t = madd(a[u].x, gx[u][0], acc);
-                acc = (unsigned)(rel[u] + 0) < (unsigned)len[u] ? t : acc;
-                t = madd(a[u].y, gx[u][1], acc);
-                acc = (unsigned)(rel[u] + 1) < (unsigned)len[u] ? t : acc;
-                t = madd(b[u].x, gx[u][2], acc);
-                acc = (unsigned)(rel[u] + 2) < (unsigned)len[u] ? t : acc;
-                t = madd(b[u].y, gx[u][3], acc);
-                acc = (unsigned)(rel[u] + 3) < (unsigned)len[u] ? t : acc;
-                // rows longer than one chunk of the group: the rest in order
-                const int e = j0[u] - rel[u] + len[u];  // the row's end
-                for (int jj = j0[u] + 4 * L; jj < e; jj += 4 * L) {
-                    const i32x4 cc = ld_stream4((const int32_t *)at_bytes<O32>(cb, jj, 4));
-                    const int vj = vpos(jj);
-                    const f64x2 v01 = ld_stream2((const double *)at_bytes<O32>(vb, vj, 8));
-                    const f64x2 v23 = ld_stream2((const double *)at_bytes<O32>(vb, vj + vstep, 8));
-                    const double x0 = ldx(cc.x), x1 = ldx(cc.y), x2 = ldx(cc.z), x3 = ldx(cc.w);
-                    acc = madd(v01.x, x0, acc);
-                    t = madd(v01.y, x1, acc);
-                    acc = jj + 1 < e ? t : acc;
-                    t = madd(v23.x, x2, acc);
-                    acc = jj + 2 < e ? t : acc;
-                    t = madd(v23.y, x3, acc);
-                    acc = jj + 3 < e ? t : acc;
-                }
-                acc = group_sum_dpp<L>(acc);
-                if (gl == 0) ysl[wv][(st + u) * R + g] = acc;
-            }
-        }
+        CsrBatch<L, U> B;
+        csr_batch_load(B, A, rpl, rpe, st);
+        csr_batch_sum(B, A, xg, ysl[wv], st);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (rl < m) __builtin_nontemporal_store(ysl[wv][lane], y + rl);
+    csr_slab_store(ysl[wv], y, r0, m);
 }
 
 // csr_slabx<L, U, S, O32>: csr_slab2 for matrices whose rows stay near the
@@ -208,28 +292,17 @@ __global__ __launch_bounds__(256) void csr_slab2_kernel(int64_t m, const RP *__r
 // stream -- which lets the stream run one batch ahead: batch i + 1's loads
 // (the next slab's first one included) are in flight while batch i's x reads
 // and adds run (A / B ping-pong, as BIN's kernels), and the first batch is
-// issued before the window is staged.  Same chunks, same order, same
-// butterfly as csr_slab2: bit-identical y.  Lanes whose loaded entry lies
+// issued before the window is staged.  Lanes whose loaded entry lies
 // outside the window (masked entries of a neighbouring row) read a clamped,
 // in-window slot.
-template <int L, int U>
-struct CsrBatch {
-    i32x4 c[U];
-    f64x2 a[U], b[U];
-    int s[U], len[U];  // the row's start (relative to the wave's base) and length
-    bool full;
-};
-
 template <int L, typename RP, int U, int S, bool O32>
 __device__ __forceinline__ void csr_slabx_body(int64_t m, const RP *__restrict__ rp, const int32_t *__restrict__ col,
                                                const double *__restrict__ val, const double *__restrict__ x,
                                                double *__restrict__ y, const int32_t *__restrict__ win0, int32_t win,
                                                int64_t n, bool vh, double *xs, double (*ysl)[64]) {
-    constexpr int R = 64 / L;   // rows per step
     constexpr int NB = L / U;   // batches per slab
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    const int g = lane / L, gl = lane & (L - 1);
     // the wave's slabs: rows r0 + 64 k, k < S (r0 >= m: no rows, but the wave
     // still helps stage the window and meets the barrier)
     const int64_t r0 = ((int64_t)blockIdx.x * 4 + wv) * 64 * S;
@@ -242,31 +315,9 @@ __device__ __forceinline__ void csr_slabx_body(int64_t m, const RP *__restrict__
         rpl[k] = (int)((int64_t)rp[rk < m ? rk : m] - base);
         rpe[k] = (int)((int64_t)rp[ek < m ? ek : m] - base);
     }
-    const int32_t *cb = col + base;
-    const int64_t vbase = vh ? base & ~(int64_t)255 : base;
-    const double *vb = val + vbase;
-    const int vo = (int)(base - vbase), vstep = vh ? 128 : 2;
-    auto vpos = [&](int j) -> int { return vh ? csr_vpos(j + vo) : j; };
+    const CsrStream<O32> A(col, val, base, vh);
     auto load = [&](CsrBatch<L, U> &B, int i) {  // batch i: slab i / NB, steps (i % NB) U ..
-        const int k = i / NB, st = (i % NB) * U;
-        B.full = true;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int li = (st + u) * R + g;
-            const int s = __shfl(rpl[k], li, 64);
-            const int nx = __shfl(rpl[k], (li + 1) & 63, 64);
-            const int e = li == 63 ? rpe[k] : nx;
-            const int a0 = s & ~3;
-            B.s[u] = s;
-            B.len[u] = e - s;
-            B.full = B.full && (s & 3) == 0 && B.len[u] == 4 * L;
-            const int j0 = a0 + 4 * gl;
-            const int jl = j0 < e ? j0 : a0;
-            B.c[u] = ld_stream4((const int32_t *)at_bytes<O32>(cb, jl, 4));
-            const int vj = vpos(jl);
-            B.a[u] = ld_stream2((const double *)at_bytes<O32>(vb, vj, 8));
-            B.b[u] = ld_stream2((const double *)at_bytes<O32>(vb, vj + vstep, 8));
-        }
+        csr_batch_load(B, A, rpl[i / NB], rpe[i / NB], (i % NB) * U);
     };
     // the workgroup's window: the union of its S granules' (win0: per
     // 256-row granule, INT32_MAX when a granule has no entries)
@@ -284,63 +335,9 @@ __device__ __forceinline__ void csr_slabx_body(int64_t m, const RP *__restrict__
         return xs[i < wmax ? i : wmax];
     };
     auto compute = [&](const CsrBatch<L, U> &B, int i) {
-        const int k = i / NB, st = (i % NB) * U;
-        double gx[U][4];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            gx[u][0] = xw(B.c[u].x);
-            gx[u][1] = xw(B.c[u].y);
-            gx[u][2] = xw(B.c[u].z);
-            gx[u][3] = xw(B.c[u].w);
-        }
-        const bool all_full = __ballot(!B.full) == 0;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            double acc = 0.0, t;
-            if (all_full) {
-                acc = madd(B.a[u].x, gx[u][0], acc);
-                acc = madd(B.a[u].y, gx[u][1], acc);
-                acc = madd(B.b[u].x, gx[u][2], acc);
-                acc = madd(B.b[u].y, gx[u][3], acc);
-            } else {
-                // positions of the lane's 4 entries relative to the row start
-                const int a0 = B.s[u] & ~3;
-                const int ra = a0 + 4 * gl - B.s[u];
-                const int rb = ra + 2;
-                t = madd(B.a[u].x, gx[u][0], acc);
-                acc = (unsigned)(ra + 0) < (unsigned)B.len[u] ? t : acc;
-                t = madd(B.a[u].y, gx[u][1], acc);
-                acc = (unsigned)(ra + 1) < (unsigned)B.len[u] ? t : acc;
-                t = madd(B.b[u].x, gx[u][2], acc);
-                acc = (unsigned)(rb + 0) < (unsigned)B.len[u] ? t : acc;
-                t = madd(B.b[u].y, gx[u][3], acc);
-                acc = (unsigned)(rb + 1) < (unsigned)B.len[u] ? t : acc;
-                const int e = B.s[u] + B.len[u];  // the row's end
-                // rows longer than one chunk of the group: the rest in order
-                for (int jj = a0 + 4 * gl + 4 * L; jj < e; jj += 4 * L) {
-                    const i32x4 cc = ld_stream4((const int32_t *)at_bytes<O32>(cb, jj, 4));
-                    const int vj = vpos(jj);
-                    const f64x2 v01 = ld_stream2((const double *)at_bytes<O32>(vb, vj, 8));
-                    const f64x2 v23 = ld_stream2((const double *)at_bytes<O32>(vb, vj + vstep, 8));
-                    const double x0 = xw(cc.x), x1 = xw(cc.y), x2 = xw(cc.z), x3 = xw(cc.w);
-                    acc = madd(v01.x, x0, acc);
-                    t = madd(v01.y, x1, acc);
-                    acc = jj + 1 < e ? t : acc;
-                    t = madd(v23.x, x2, acc);
-                    acc = jj + 2 < e ? t : acc;
-                    t = madd(v23.y, x3, acc);
-                    acc = jj + 3 < e ? t : acc;
-                }
-            }
-            acc = group_sum_dpp<L>(acc);
-            if (gl == 0) ysl[wv][(st + u) * R + g] = acc;
-        }
-        if (i % NB == NB - 1) {  // the slab is done: its 64 sums leave in one coalesced store
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const int64_t rl = r0 + 64 * k + lane;
-            if (rl < m) __builtin_nontemporal_store(ysl[wv][lane], y + rl);
+        csr_batch_sum(B, A, xw, ysl[wv], (i % NB) * U);
+        if (i % NB == NB - 1) {  // the slab is done; ysl[wv] is free again after the store
+            csr_slab_store(ysl[wv], y, r0 + 64 * (i / NB), m);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -348,7 +345,7 @@ __device__ __forceinline__ void csr_slabx_body(int64_t m, const RP *__restrict__
     };
     // the wave's batches: all S slabs while their rows exist
     const int nb = r0 >= m ? 0 : (int)std::min<int64_t>(S, (m - r0 + 63) / 64) * NB;
-    CsrBatch<L, U> A, B;
+    CsrBatch<L, U> Ba, Bb;
     // window staging: its loads go out first, then the first batch's, so
     // both are in flight together
     constexpr int XT = 4;  // window values per thread held in flight (win <= 256 XT: one pass)
@@ -358,7 +355,7 @@ __device__ __forceinline__ void csr_slabx_body(int64_t m, const RP *__restrict__
         const int i = threadIdx.x + q * 256;
         t[q] = i < win ? x[c0 + i < n ? c0 + i : n - 1] : 0.0;
     }
-    if (nb > 0) load(A, 0);
+    if (nb > 0) load(Ba, 0);
 #pragma unroll
     for (int q = 0; q < XT; ++q) {
         const int i = threadIdx.x + q * 256;
@@ -367,11 +364,11 @@ __device__ __forceinline__ void csr_slabx_body(int64_t m, const RP *__restrict__
     for (int i = threadIdx.x + XT * 256; i < win; i += 256) xs[i] = x[c0 + i < n ? c0 + i : n - 1];
     __syncthreads();
     for (int i = 0; i < nb; i += 2) {
-        if (i + 1 < nb) load(B, i + 1);
-        compute(A, i);
+        if (i + 1 < nb) load(Bb, i + 1);
+        compute(Ba, i);
         if (i + 1 >= nb) break;
-        if (i + 2 < nb) load(A, i + 2);
-        compute(B, i + 1);
+        if (i + 2 < nb) load(Ba, i + 2);
+        compute(Bb, i + 1);
     }
 }
 
@@ -399,8 +396,6 @@ struct CsrBinTable {
 // the short-row bins fill in behind them instead of forming the tail
 constexpr int kCsrLaunchOrder[kCsrBins] = {7, 6, 5, 4, 3, 2, 1, 0};
 
-// ADD: y[yrow[row]] += sum (the HYB/JDS overflow, one writer per row);
-// otherwise y[row] = sum
 template <int L, typename RP, bool ADD>
 __device__ __forceinline__ void csr_rows_body(int64_t wg, int64_t nrows, const int32_t *__restrict__ rows,
                                               const RP *__restrict__ rp, const int32_t *__restrict__ col,
@@ -410,31 +405,8 @@ __device__ __forceinline__ void csr_rows_body(int64_t wg, int64_t nrows, const i
     const int lane = threadIdx.x & (L - 1);
     if (g >= nrows) return;
     const int64_t row = rows[g];
-    const int64_t s = rp[row];
-    const int64_t e = rp[row + 1];
-    double acc = 0.0;
-    for (int64_t j = (s & ~(int64_t)3) + 4 * lane; j < e; j += 4 * L) {
-        const i32x4 c = ld_stream4(col + j);
-        const f64x2 v01 = ld_stream2(val + j);
-        const f64x2 v23 = ld_stream2(val + j + 2);
-        const double x0 = (j + 0 >= s && j + 0 < e) ? ld_x(x, c.x) : 0.0;
-        const double x1 = (j + 1 >= s && j + 1 < e) ? ld_x(x, c.y) : 0.0;
-        const double x2 = (j + 2 >= s && j + 2 < e) ? ld_x(x, c.z) : 0.0;
-        const double x3 = (j + 3 >= s && j + 3 < e) ? ld_x(x, c.w) : 0.0;
-        if (j + 0 >= s && j + 0 < e) acc = madd(v01.x, x0, acc);
-        if (j + 1 >= s && j + 1 < e) acc = madd(v01.y, x1, acc);
-        if (j + 2 >= s && j + 2 < e) acc = madd(v23.x, x2, acc);
-        if (j + 3 >= s && j + 3 < e) acc = madd(v23.y, x3, acc);
-    }
-    acc = group_sum<L>(acc);
-    if (lane == 0) {
-        if (ADD) {
-            const int64_t yi = yrow[row];
-            y[yi] = __dadd_rn(y[yi], acc);
-        } else {
-            y[row] = acc;
-        }
-    }
+    const double acc = group_sum<L>(csr_row_sum<L>(rp[row], rp[row + 1], lane, col, val, x, false));
+    if (lane == 0) csr_store_row<ADD>(y, yrow, row, acc);
 }
 
 template <typename RP, bool ADD>
@@ -463,30 +435,12 @@ __global__ __launch_bounds__(256) void csr_adaptive_kernel(CsrBinTable t, const 
         default: {
             // one workgroup per row: four wave sums added in wave order
             const int64_t row = br[wg];
-            const int64_t s = rp[row];
-            const int64_t e = rp[row + 1];
-            double acc = 0.0;
-            for (int64_t j = (s & ~(int64_t)3) + 4 * threadIdx.x; j < e; j += 4 * 256) {
-                const i32x4 c = ld_stream4(col + j);
-                const f64x2 v01 = ld_stream2(val + j);
-                const f64x2 v23 = ld_stream2(val + j + 2);
-                if (j + 0 >= s && j + 0 < e) acc = madd(v01.x, ld_x(x, c.x), acc);
-                if (j + 1 >= s && j + 1 < e) acc = madd(v01.y, ld_x(x, c.y), acc);
-                if (j + 2 >= s && j + 2 < e) acc = madd(v23.x, ld_x(x, c.z), acc);
-                if (j + 3 >= s && j + 3 < e) acc = madd(v23.y, ld_x(x, c.w), acc);
-            }
-            acc = group_sum<64>(acc);
+            const double acc =
+                group_sum<64>(csr_row_sum<256>(rp[row], rp[row + 1], (int)threadIdx.x, col, val, x, false));
             if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
             __syncthreads();
-            if (threadIdx.x == 0) {
-                const double sum = __dadd_rn(__dadd_rn(part[0], part[1]), __dadd_rn(part[2], part[3]));
-                if (ADD) {
-                    const int64_t yi = yrow[row];
-                    y[yi] = __dadd_rn(y[yi], sum);
-                } else {
-                    y[row] = sum;
-                }
-            }
+            if (threadIdx.x == 0)
+                csr_store_row<ADD>(y, yrow, row, __dadd_rn(__dadd_rn(part[0], part[1]), __dadd_rn(part[2], part[3])));
         }
     }
 }
@@ -549,9 +503,9 @@ static void launch_slab_u(const spmv_plan_s *p, int kind, size_t lds, const doub
         int S = kCsrSlabsPerWave;
 #ifdef SPMV_PROBES
         if (const char *e = probe_env("SPMV_LAUNCH_CSR_S")) S = std::atoi(e);
-        if (!c.win_s[S == 4 ? 2 : S == 1 ? 0 : 1]) S = kCsrSlabsPerWave;
+        if (!c.win_s[csr_win_index(S)]) S = kCsrSlabsPerWave;
 #endif
-        const int32_t win = c.win_s[S == 4 ? 2 : S == 1 ? 0 : 1];
+        const int32_t win = c.win_s[csr_win_index(S)];
         const size_t wl = std::max(lds, sizeof(double) * (size_t)win);
         const unsigned grid = (unsigned)((p->m + 256 * S - 1) / (256 * S));
         auto go = [&](auto kern) {
@@ -575,12 +529,12 @@ static void launch_slab_u(const spmv_plan_s *p, int kind, size_t lds, const doub
 #endif
         return;
     }
-    if (p->csr.off32)
-        hipLaunchKernelGGL((csr_slab2_kernel<L, RP, UU, true>), dim3((unsigned)((waves + 3) / 4)), dim3(256), lds,
-                           p->stream, p->m, (const RP *)p->csr.row_ptr, p->csr.col, p->csr.val, x, y, c.val_halves);
-    else
-        hipLaunchKernelGGL((csr_slab2_kernel<L, RP, UU, false>), dim3((unsigned)((waves + 3) / 4)), dim3(256), lds,
-                           p->stream, p->m, (const RP *)p->csr.row_ptr, p->csr.col, p->csr.val, x, y, c.val_halves);
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)((waves + 3) / 4)), dim3(256), lds, p->stream, p->m,
+                           (const RP *)c.row_ptr, c.col, c.val, x, y, c.val_halves);
+    };
+    if (c.off32) go(csr_slab2_kernel<L, RP, UU, true>);
+    else go(csr_slab2_kernel<L, RP, UU, false>);
 }
 
 // The product instantiates only the default shape (CsrLaunch{}: slab 3, U =
@@ -642,48 +596,12 @@ int launch_csr(const spmv_plan_s *p, const double *x, double *y) {
     return p->csr.rp64 ? launch_csr_rp<int64_t>(p, x, y) : launch_csr_rp<int32_t>(p, x, y);
 }
 
-// ---- HYB overflow: CSR-vector over the overflow rows, y[row] += sum -------
-template <int L>
-__global__ __launch_bounds__(256) void hyb_overflow_kernel(int64_t nrows, const int32_t *__restrict__ rows,
-                                                           const int64_t *__restrict__ rp,
-                                                           const int32_t *__restrict__ col,
-                                                           const double *__restrict__ val,
-                                                           const double *__restrict__ x,
-                                                           double *__restrict__ y) {
-    const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t r = gtid / L;
-    const int lane = threadIdx.x & (L - 1);
-    if (r >= nrows) return;
-    const int64_t s = rp[r];
-    const int64_t e = rp[r + 1];
-    double acc = 0.0;
-    for (int64_t j = (s & ~(int64_t)3) + 4 * lane; j < e; j += 4 * L) {
-        const i32x4 c = ld_stream4(col + j);
-        const f64x2 v01 = ld_stream2(val + j);
-        const f64x2 v23 = ld_stream2(val + j + 2);
-        if (j + 0 >= s && j + 0 < e) acc = madd(v01.x, ld_x(x, c.x), acc);
-        if (j + 1 >= s && j + 1 < e) acc = madd(v01.y, ld_x(x, c.y), acc);
-        if (j + 2 >= s && j + 2 < e) acc = madd(v23.x, ld_x(x, c.z), acc);
-        if (j + 3 >= s && j + 3 < e) acc = madd(v23.y, ld_x(x, c.w), acc);
-    }
-    acc = group_sum<L>(acc);
-    if (lane == 0) {
-        const int32_t row = rows[r];
-        y[row] = __dadd_rn(y[row], acc);  // single writer per row
-    }
-}
-
+// HYB / JDS overflow: the adaptive kernel over the overflow rows binned by
+// their overflow length, y[row] += sum.  Every plan with overflow rows has
+// the bins (overflow_upload_index, formats.cpp); none: no workgroups, no launch.
 int launch_hyb_overflow(const spmv_plan_s *p, const double *x, double *y) {
     const HybDev &h = p->hyb;
-    if (h.n_rows == 0) return SPMV_SUCCESS;
-    if (h.bin_rows)  // overflow rows binned by their overflow length
-        return launch_adaptive<int64_t, true>(p, h.bin_off, h.bin_rows, h.row_ptr, h.col, h.val, x, y, h.rows);
-    const int L = 64;
-    const int64_t blocks = (h.n_rows * L + 255) / 256;
-    hipLaunchKernelGGL((hyb_overflow_kernel<64>), dim3((unsigned)blocks), dim3(256), 0, p->stream,
-                       h.n_rows, h.rows, h.row_ptr, h.col, h.val, x, y);
-    SPMV_HIP_TRY(hipGetLastError());
-    return SPMV_SUCCESS;
+    return launch_adaptive<int64_t, true>(p, h.bin_off, h.bin_rows, h.row_ptr, h.col, h.val, x, y, h.rows);
 }
 
 }  // namespace spmv

@@ -204,6 +204,59 @@ def test_csr_window_kernel_small_shapes(m, n, lanes):
         check_close(y, yo, what=f"{m}x{n}")
 
 
+@pytest.mark.parametrize("lanes", [1, 4, 16, 64])
+@pytest.mark.parametrize("shape", ["full", "shifted", "long"])
+def test_csr_slab_batch_branches(shape, lanes):
+    """Every branch of the slab batch (csr_batch_load / csr_batch_sum of
+    k_csr.hip) through both kernels that share it.  600 rows: a partial last
+    slab and a partial last 256-row granule; n = m + 600 columns.
+    full: row r holds exactly the 4 lanes columns r .. r + 4 lanes - 1, every
+    row one aligned chunk -- the unmasked adds (the last slab's missing rows
+    put one batch through the masked ones);
+    shifted: as full with one more entry in row 0, so every later row start
+    is misaligned (masked adds, no tail) and row 0 takes one tail iteration;
+    long: 9 lanes + 3 consecutive columns from r, every 7th row empty (two or
+    three tail iterations, empty rows).
+    The band is at most 579 columns wide, so the plan has x windows
+    (csr_slabx).  The same rows with one explicit 0.0 far off the band in the
+    last row leave no window (csr_slab2): with n = 1200 <= kCsrMaxWin = 4096
+    no column of the matrix itself is far enough, so that plan is kCsrMaxWin
+    columns wider and the zero sits in its last column.  All rows but the
+    last are bit-identical between the two kernels."""
+    m, max_win = 600, 4096
+    n = m + 600
+    rng = np.random.default_rng(600 + lanes)
+    if shape == "long":
+        lens = np.full(m, 9 * lanes + 3)
+        lens[6::7] = 0
+    else:
+        lens = np.full(m, 4 * lanes)
+        if shape == "shifted":
+            lens[0] += 1
+    rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    rows = np.repeat(np.arange(m), lens)
+    col = (rows + np.arange(int(rp[-1])) - rp[rows]).astype(np.int32)  # consecutive from r
+    assert lens[-1] > 0 and int(col.max()) < n and int((col - rows).max()) < 579
+    val = rng.random(len(col)) + 0.5
+    x = rng.random(n + max_win)
+    plan = sp.Plan.from_csr(m, n, rp, col, val, "csr", csr_lanes=lanes)
+    assert plan.info()["kernel"].startswith("csr_slabx_kernel"), plan.info()["kernel"]
+    y = run_plan(plan, x[:n], m)
+    yo = oracle_y(rp, col, val, x[:n])
+    col2 = np.concatenate([col, [n + max_win - 1]]).astype(np.int32)
+    val2 = np.concatenate([val, [0.0]])
+    rp2 = rp.copy()
+    rp2[-1] += 1
+    plan2 = sp.Plan.from_csr(m, n + max_win, rp2, col2, val2, "csr", csr_lanes=lanes)
+    assert plan2.info()["kernel"].startswith("csr_slab2_kernel"), plan2.info()["kernel"]
+    y2 = run_plan(plan2, x, m)
+    assert np.array_equal(y[:-1], y2[:-1])
+    check_close(y, yo, what=f"slabx {shape} lanes {lanes}")
+    check_close(y2, yo, what=f"slab2 {shape} lanes {lanes}")
+    if lanes == 1:
+        assert np.array_equal(y, yo) and np.array_equal(y2, yo)
+
+
 @pytest.mark.parametrize("sigma", [4, 8, 12, 16, 20, 24, 32, 48, 64])
 @pytest.mark.parametrize("kind", ["powerlaw", "uniform", "empty_rows", "banded", "short"])
 def test_ss_sigma(sigma, kind):
