@@ -36,7 +36,9 @@
  * is idempotent -- repeated calls give identical y (the two-call verification
  * of src/main.cpp:41-55).  Host input arrays are borrowed read-only during
  * plan creation and never mutated (unlike the CSR5 handle, which transposes
- * the caller's arrays in place, CSR5_cuda/anonymouslib_cuda.h:203-204).
+ * the caller's arrays in place, CSR5_cuda/anonymouslib_cuda.h:203-204).  A
+ * plan's sparsity pattern is frozen at creation; its values are not:
+ * spmv_plan_update_values rewrites them in place (below, "value refresh").
  *
  * Non-finite and subnormal values: every product and every sum is an IEEE
  * binary64 operation, round to nearest, with gradual underflow -- nothing is
@@ -78,7 +80,8 @@ extern "C" {
  * (spmv_options_default) keeps the version-3 results (build = AUTO moves only
  * where the layout is made, not what it is).  The multi-vector entry points
  * (spmv_execute_multi, spmv_time_multi, spmv_multi_path) are new functions
- * and change no struct: the version stays 3.  Callers may
+ * and change no struct: the version stays 3.  So do the value-refresh entry
+ * points (spmv_plan_update_prepare, spmv_plan_update_values).  Callers may
  * check spmv_api_version() == SPMV_HIP_API_VERSION once at startup; the
  * structs are only ever filled by spmv_options_default / spmv_plan_info of a
  * library with the same version. */
@@ -409,6 +412,84 @@ int spmv_time_multi(spmv_plan_t plan, int32_t k, const double *X_dev, int64_t ld
 int spmv_multi_path(spmv_plan_t plan, int32_t k, const double *X, int64_t ldx,
                     const double *Y, int64_t ldy, uint32_t flags,
                     int32_t *widths, int32_t cap, int32_t *n_blocks);
+
+/* ---- value refresh: new values on a fixed sparsity pattern -----------------
+ * Every layout decision of a plan (the format AUTO picks, slices, bins,
+ * strips, tiles, windows, overflow rows, CSS lists) depends on (row_ptr,
+ * col_idx) alone, so new values on the same pattern need no rebuild:
+ * spmv_plan_update_prepare learns once where every CSR entry lives in the
+ * plan's layout, spmv_plan_update_values then rewrites the value arrays.
+ *
+ * "The CSR the plan was created from" is the (row_ptr, col_idx) handed to
+ * spmv_plan_create_csr / _csr32 (row pointers widened) / _csr_device; for
+ * spmv_plan_create_coo it is the sorted COO as passed: its entry order and
+ * spmv_coo_to_csr's row pointers.
+ *
+ * In place.  No device pointer of the plan changes: HIP graphs created before
+ * an update replay the new values, fused and generic multi executes see them,
+ * and the placement the plan drew at creation (VMM, SEARCH) is kept.
+ *
+ * Nothing but values moves.  The update rewrites CSR `val`, SS `val`,
+ * ELL / HYB / JDS `ell_val` and `ovf_val`, DIA `val`, COO `val`, CSS `val` and
+ * BIN `val1` (the names of spmv_plan_digest_name); every other array keeps
+ * its digest.  Afterwards the plan is, byte for byte, the plan a fresh create
+ * with these values and the same options would give.
+ *
+ * Padding stays what the builder wrote: +0.0 in ELL and DIA padding, the
+ * kPad tails, BIN voids and slack, CSS and COO unit padding and SS tile
+ * tails.  A NaN or Inf in val reaches only its own slot.  Where a builder
+ * stores a function of the value, the refresh applies the same function: DIA
+ * adds each entry into a +0.0 slot, so a -0.0 value is stored as +0.0.
+ *
+ * Refusals come before any device work, in this order: flag bits other than
+ * the ones named at each function; a NULL plan; a NULL row_ptr, or a NULL
+ * col_idx / val with nnz > 0; SPMV_ASYNC without SPMV_VAL_DEVICE -- all
+ * SPMV_ERROR_INVALID_VALUE; then spmv_plan_update_values on a plan that was
+ * not prepared: SPMV_ERROR_INVALID_VALUE, "not prepared" in spmv_last_error.
+ *
+ * Wrong pattern.  Prepare rebuilds the layout from the pattern it is given
+ * (a transient shadow plan: the plan's resolved options, PLAIN placement,
+ * values 1, 2, .., nnz) and compares every non-value array with the plan's
+ * by digest; the plan's current non-zero values must also sit on slots the
+ * pattern fills.  A pattern that does not reproduce the plan's layout returns
+ * SPMV_ERROR_INVALID_VALUE with a message about the pattern; the plan stays
+ * unprepared and fully usable.  (DIA stores no column indices: there the check
+ * sees the diagonal offsets and the slots of the current non-zero values.)
+ *
+ * Layouts that merge entries.  Prepare succeeds only if every source index
+ * 0 .. nnz-1 appears exactly once among the layout's value slots.  A DIA plan
+ * built from rows with duplicate (row, col) entries adds several values into
+ * one slot: no one-source-per-slot map exists, prepare returns
+ * SPMV_ERROR_NOT_SUPPORTED and the plan stays usable (and unprepared).
+ *
+ * Empty plans (nnz = 0 or m = 0): both calls succeed and do nothing.
+ *
+ * Memory.  The map holds 4 bytes per value slot (8 where nnz >= 2^31 - 1),
+ * allocated at prepare, counted in spmv_plan_info.device_bytes and freed with
+ * the plan.  A host val is staged through a plan-owned buffer of nnz doubles,
+ * allocated at the first host update; SPMV_ERROR_OUT_OF_MEMORY there leaves
+ * the plan usable and its values untouched.  Prepare itself holds a second
+ * plan and a device copy of the pattern while it runs.
+ *
+ * The drop-in (opt_hip.h), the CSR5 handle and spmv_dist_* have no update
+ * form. */
+#define SPMV_CSR_DEVICE 0x20u /* row_ptr / col_idx are device pointers on the plan's device */
+#define SPMV_VAL_DEVICE 0x40u /* val is a device pointer on the plan's device               */
+
+/* Teach the plan where every entry of the CSR it was created from lives in its
+ * layout.  row_ptr (m + 1, int64) and col_idx (nnz) must be the pattern the
+ * plan was built from, in the same entry order.  Costs about one plan build,
+ * once.  Calling it again on a prepared plan is a cheap success (the pattern
+ * is not looked at again).  Flags: SPMV_CSR_DEVICE. */
+int spmv_plan_update_prepare(spmv_plan_t plan, const int64_t *row_ptr,
+                             const int32_t *col_idx, uint32_t flags);
+
+/* Replace the plan's values by val[0 .. nnz), in the order of that CSR.  The
+ * plan's value arrays are rewritten in place, on the plan's stream.  Flags:
+ * SPMV_VAL_DEVICE, and SPMV_ASYNC (device val only: return without
+ * synchronising; val must stay valid until the stream has passed the update).
+ * A device val needs the 8-byte alignment of a double, no more. */
+int spmv_plan_update_values(spmv_plan_t plan, const double *val, uint32_t flags);
 
 /* ---- HIP graph of the device-resident execute -----------------------------
  * The plan's launch sequence for (x_dev -> y_dev), captured `reps` times in a

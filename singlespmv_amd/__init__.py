@@ -40,6 +40,7 @@ OPT_LIB_PATH = os.path.join(HERE, "libopt_hip.so")
 FORMATS = {"auto": 0, "csr": 1, "crs": 1, "ell": 2, "ss": 3, "dia": 4, "hyb": 5, "css": 6, "coo": 7, "jds": 8, "bin": 9}
 FORMAT_NAMES = {0: "auto", 1: "csr", 2: "ell", 3: "ss", 4: "dia", 5: "hyb", 6: "css", 7: "coo", 8: "jds", 9: "bin"}
 X_DEVICE, Y_DEVICE, ASYNC, X_STAGED, Y_STAGED = 0x1, 0x2, 0x4, 0x8, 0x10
+CSR_DEVICE, VAL_DEVICE = 0x20, 0x40  # spmv_plan_update_prepare / spmv_plan_update_values
 GEN_UNIFORM, GEN_POWERLAW, GEN_BANDED = 1, 2, 3
 API_VERSION = 3  # SPMV_HIP_API_VERSION of the structs mirrored here
 
@@ -110,6 +111,7 @@ EXPORTS = [
     "spmv_plan_digest", "spmv_plan_digest_name", "spmv_dist_shard", "spmv_dist_assemble",
     "spmv_fetch_y", "spmv_dist_fetch_y", "spmv_plan_built_on_device",
     "spmv_execute_multi", "spmv_time_multi", "spmv_multi_path",
+    "spmv_plan_update_prepare", "spmv_plan_update_values",
 ]
 
 _lib = None
@@ -147,6 +149,8 @@ def lib():
     L.spmv_execute_multi.argtypes = [vp, i32, vp, i64, vp, i64, C.c_uint32]
     L.spmv_time_multi.argtypes = [vp, i32, vp, i64, vp, i64, i32, C.POINTER(f64)]
     L.spmv_multi_path.argtypes = [vp, i32, vp, i64, vp, i64, C.c_uint32, C.POINTER(i32), i32, C.POINTER(i32)]
+    L.spmv_plan_update_prepare.argtypes = [vp, vp, vp, C.c_uint32]
+    L.spmv_plan_update_values.argtypes = [vp, vp, C.c_uint32]
     L.spmv_dist_fetch_y.argtypes = [vp, vp]
     L.spmv_plan_create_csr32_device.argtypes = [i32, i32, i32, vp, vp, vp, C.POINTER(Options), C.POINTER(vp)]
     L.spmv_set_stream.argtypes = [vp, vp]
@@ -615,6 +619,41 @@ class Plan:
         _check(lib().spmv_multi_path(self._h, k, _ptr(X), ldx, _ptr(Y), ldy, flags, w, MULTI_MAX, C.byref(nb)),
                "spmv_multi_path")
         return [int(w[b]) for b in range(nb.value)]
+
+    # value refresh ----------------------------------------------------------
+    def prepare_update(self, row_ptr, col) -> None:
+        """Teach the plan where every entry of the CSR it was created from
+        lives in its layout (spmv_plan_update_prepare; about one plan build,
+        once).  row_ptr / col: the pattern the plan was built from, as numpy
+        arrays (like from_csr) or CUDA tensors (like from_device_csr)."""
+        nnz = self.info()["nnz"]
+        if _is_device(row_ptr) or _is_device(col):
+            for name, t, dt, need in (("row_ptr", row_ptr, torch.int64, self.m + 1), ("col", col, torch.int32, nnz)):
+                if not _is_device(t) or t.dtype != dt or not t.is_contiguous():
+                    raise ValueError(f"{name} must be a contiguous {dt} CUDA tensor")
+                if t.device.index != self.device:
+                    raise ValueError(f"{name} is on cuda:{t.device.index}, the plan on cuda:{self.device}")
+                if t.numel() < need:
+                    raise ValueError(f"{name} holds {t.numel()} entries, the plan needs {need}")
+            flags = CSR_DEVICE
+        else:
+            row_ptr = np.ascontiguousarray(row_ptr, np.int64)
+            col = np.ascontiguousarray(col, np.int32)
+            if row_ptr.size < self.m + 1 or col.size < nnz:
+                raise ValueError(f"row_ptr / col hold {row_ptr.size} / {col.size} entries, "
+                                 f"the plan needs {self.m + 1} / {nnz}")
+            flags = 0
+        _check(lib().spmv_plan_update_prepare(self._h, _ptr(row_ptr), _ptr(col), flags), "spmv_plan_update_prepare")
+
+    def update_values(self, val, async_: bool = False) -> None:
+        """Replace the plan's values by val (nnz float64, in the order of the
+        CSR the plan was created from), in place on the plan's stream
+        (spmv_plan_update_values).  A numpy array is a host buffer, a CUDA
+        tensor a device buffer (8-byte alignment is enough); async_ needs a
+        device buffer."""
+        _check_vec(val, self.info()["nnz"], "val", self.device, writable=False)
+        flags = (VAL_DEVICE if _is_device(val) else 0) | (ASYNC if async_ else 0)
+        _check(lib().spmv_plan_update_values(self._h, _ptr(val), flags), "spmv_plan_update_values")
 
     def __call__(self, x, y=None):
         if y is None:

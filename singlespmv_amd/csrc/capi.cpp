@@ -9,7 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "internal.hpp"
+#include "build_util.hpp"
 
 namespace spmv {
 
@@ -96,6 +96,16 @@ static const FormatBuilders *builders_for(int fmt) {
     if (fmt > SPMV_FORMAT_AUTO && fmt <= SPMV_FORMAT_BIN) return &kBuilders[fmt];
     set_error("unknown format");
     return nullptr;
+}
+
+// The options a finished plan keeps (spmv_plan_s::opts): `o` as the create
+// path ended with it (choose_crs_exact's rewrites applied), the format built,
+// the plan's device; crs_exact itself is resolved, so it is cleared.
+static void keep_options(spmv_plan_s *p, const spmv_options_t &o, int fmt, int dev) {
+    p->opts = o;
+    p->opts.format = fmt;
+    p->opts.device = dev;
+    p->opts.crs_exact = 0;
 }
 
 // Validate a host CSR before anything touches the GPU: an out-of-range
@@ -216,6 +226,7 @@ static int create_device_impl(int64_t m, int64_t n, int64_t nnz, const int64_t *
     if (st == SPMV_SUCCESS && !host_build) {
         p->format = fmt;
         p->built_on_device = 1;
+        keep_options(p, o, fmt, dev);
         *out = p;
         return SPMV_SUCCESS;
     }
@@ -320,6 +331,7 @@ static int create_from_csr(const HostCsr &A, const spmv_options_t *opt_in, spmv_
         return st;
     }
     p->format = fmt;
+    keep_options(p, o, fmt, dev);
     *out = p;
     return SPMV_SUCCESS;
 }
@@ -725,6 +737,99 @@ int spmv_time_multi(spmv_plan_t p, int32_t k, const double *X_dev, int64_t ldx, 
     SPMV_RETURN_IF(bind_device(p));
     p->y_staged = false;
     return time_on_stream(p->stream, iters, ms, [&] { return multi_dispatch(p, k, X_dev, ldx, Y_dev, ldy); });
+}
+
+}  // extern "C"
+
+// ---- value refresh (new values on the plan's pattern; kernels: k_update.hip) --
+extern "C" {
+
+int spmv_plan_update_prepare(spmv_plan_t p, const int64_t *row_ptr, const int32_t *col_idx, uint32_t flags) {
+    SPMV_CHECK_ARG(!(flags & ~SPMV_CSR_DEVICE), "spmv_plan_update_prepare: flag bits other than SPMV_CSR_DEVICE");
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    SPMV_CHECK_ARG(row_ptr != nullptr, "row_ptr is NULL");
+    SPMV_CHECK_ARG(p->nnz == 0 || col_idx != nullptr, "col_idx is NULL");
+    if (p->upd.prepared) return SPMV_SUCCESS;
+    if (p->nnz == 0 || p->m == 0) {
+        p->upd.prepared = true;  // nothing to map
+        return SPMV_SUCCESS;
+    }
+    SPMV_RETURN_IF(bind_device(p));
+    // the pattern in HBM (a host pattern is staged, as create_via_device does)
+    // with values 1 .. nnz; the builders run on the null stream
+    DevScratch scratch(nullptr);
+    const int64_t *d_rp = row_ptr;
+    const int32_t *d_col = col_idx;
+    if (!(flags & SPMV_CSR_DEVICE)) {
+        int64_t *rp = nullptr;
+        int32_t *col = nullptr;
+        SPMV_RETURN_IF(scratch.alloc(&rp, (size_t)p->m + 1, "row_ptr staging"));
+        SPMV_RETURN_IF(scratch.alloc(&col, (size_t)p->nnz, "col_idx staging"));
+        SPMV_HIP_TRY(hipMemcpy(rp, row_ptr, 8 * (size_t)(p->m + 1), hipMemcpyHostToDevice));
+        SPMV_HIP_TRY(hipMemcpy(col, col_idx, 4 * (size_t)p->nnz, hipMemcpyHostToDevice));
+        d_rp = rp;
+        d_col = col;
+    }
+    double *d_val = nullptr;
+    SPMV_RETURN_IF(scratch.alloc(&d_val, (size_t)p->nnz, "shadow values"));
+    SPMV_RETURN_IF(launch_iota_values(nullptr, d_val, p->nnz));
+    // the shadow: the plan's resolved options, no placement search, no VMM
+    spmv_options_t o = p->opts;
+    o.placement = SPMV_PLACEMENT_PLAIN;
+    o.build = SPMV_BUILD_DEVICE;
+    spmv_plan_t shadow = nullptr;
+    int st = create_device_impl(p->m, p->n, p->nnz, d_rp, d_col, d_val, &o, &shadow, nullptr);
+    if (st == SPMV_ERROR_INVALID_VALUE || st == SPMV_ERROR_NOT_SUPPORTED) {
+        // the plan's own build took these options: it is the pattern that differs
+        set_error(std::string("spmv_plan_update_prepare: the pattern does not reproduce the plan's layout (") +
+                  last_error() + ")");
+        st = SPMV_ERROR_INVALID_VALUE;
+    }
+    if (st != SPMV_SUCCESS) return st;
+    st = bind_device(p);
+    if (st == SPMV_SUCCESS) st = update_prepare_from_shadow(p, shadow);
+    const std::string msg = last_error();
+    (void)spmv_plan_destroy(shadow);
+    set_error(msg);
+    return st;
+}
+
+int spmv_plan_update_values(spmv_plan_t p, const double *val, uint32_t flags) {
+    SPMV_CHECK_ARG(!(flags & ~(SPMV_VAL_DEVICE | SPMV_ASYNC)),
+                   "spmv_plan_update_values: flag bits other than SPMV_VAL_DEVICE and SPMV_ASYNC");
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    SPMV_CHECK_ARG(p->nnz == 0 || val != nullptr, "val is NULL");
+    SPMV_CHECK_ARG(!(flags & SPMV_ASYNC) || (flags & SPMV_VAL_DEVICE), "SPMV_ASYNC without SPMV_VAL_DEVICE");
+    SPMV_CHECK_ARG(p->upd.prepared,
+                   "spmv_plan_update_values: plan not prepared (spmv_plan_update_prepare comes first)");
+    if (p->nnz == 0 || p->m == 0) return SPMV_SUCCESS;
+    SPMV_RETURN_IF(bind_device(p));
+    const double *d_val = val;
+    if (flags & SPMV_VAL_DEVICE) {
+        hipPointerAttribute_t a;
+        if (hipPointerGetAttributes(&a, val) != hipSuccess || a.type != hipMemoryTypeDevice || a.device != p->device) {
+            (void)hipGetLastError();
+            set_error("spmv_plan_update_values: SPMV_VAL_DEVICE needs device memory on the plan's device");
+            return SPMV_ERROR_INVALID_VALUE;
+        }
+    } else {
+        if (!p->upd.stage) {
+            // plain hipMalloc memory, like the maps (no 2-MB rounding)
+            const size_t keep = p->arena.vmm_min;
+            p->arena.vmm_min = 0;
+            void *q = nullptr;
+            const int st = p->arena.alloc(&q, sizeof(double) * (size_t)p->nnz);
+            p->arena.vmm_min = keep;
+            SPMV_RETURN_IF(st);
+            p->upd.stage = (double *)q;
+        }
+        SPMV_HIP_TRY(hipMemcpyAsync(p->upd.stage, val, sizeof(double) * (size_t)p->nnz, hipMemcpyHostToDevice,
+                                    p->stream));
+        d_val = p->upd.stage;
+    }
+    SPMV_RETURN_IF(launch_update_values(p, d_val));
+    if (!(flags & SPMV_ASYNC)) SPMV_HIP_TRY(hipStreamSynchronize(p->stream));
+    return SPMV_SUCCESS;
 }
 
 }  // extern "C"

@@ -423,6 +423,22 @@ struct BinDev {
     std::vector<float> placement_ms;  // Mul ms of each product-buffer candidate
 };
 
+// Value refresh (k_update.hip): one map per value array of the plan, in
+// plan_arrays order.  map[s] = 0: slot s is padding; else the slot holds
+// f(val[map[s] - 1]) of the CSR the plan was created from.
+struct UpdArray {
+    double *dst = nullptr;  // the plan's value array (16-byte aligned)
+    void *map = nullptr;    // int32 or int64 [slots] (UpdState::wide)
+    int64_t slots = 0;
+};
+struct UpdState {
+    bool prepared = false;
+    bool wide = false;      // 64-bit map entries (nnz >= 2^31 - 1)
+    bool dia_add = false;   // slots hold 0.0 + v (DIA's fill), not v
+    std::vector<UpdArray> arrays;
+    double *stage = nullptr;  // host val staging, nnz doubles (first host update)
+};
+
 }  // namespace spmv
 
 struct spmv_plan_s {
@@ -431,6 +447,12 @@ struct spmv_plan_s {
     int built_on_device = 0;  // 1: the layout was built in HBM (spmv_plan_create_csr_device or build AUTO/DEVICE)
     int64_t m = 0, n = 0, nnz = 0;
     hipStream_t stream = nullptr;
+    // the options the plan was built with, resolved: format = the one built
+    // (AUTO and crs_exact resolved, crs_exact's rewrites applied and the flag
+    // cleared), device = the plan's.  A second build from the same pattern
+    // with these gives the same layout (spmv_plan_update_prepare).
+    spmv_options_t opts = {};
+    spmv::UpdState upd;
     spmv::DevArena arena;
     spmv::CsrDev csr;
     spmv::EllDev ell;
@@ -627,5 +649,27 @@ int launch_ell_multi(const spmv_plan_s *p, int K, const double *X, int64_t ldx, 
 int launch_multi_copy(const spmv_plan_s *p, int64_t len, const double *src, int64_t src_ld, double *dst,
                       int64_t dst_ld);
 int launch_multi_zero(const spmv_plan_s *p, int32_t k, double *Y, int64_t ldy);
+
+// k_devbuild.hip -- the device arrays of a plan with their logical sizes, in
+// the order of spmv_plan_digest; plan_digests: their digests (synchronises)
+struct ArrayRef {
+    const char *name;
+    const void *ptr;
+    int64_t bytes;
+};
+int plan_arrays(const spmv_plan_s *p, std::vector<ArrayRef> &a);
+int plan_digests(const spmv_plan_s *p, const std::vector<ArrayRef> &a, std::vector<uint64_t> &d);
+// arrays of plan_arrays that hold matrix values (CSR / SS / DIA / COO / CSS
+// `val`, `ell_val`, `ovf_val`, BIN `val1`)
+bool is_value_array(const char *name);
+
+// k_update.hip -- value refresh.  update_prepare_from_shadow: `shadow` is a
+// plan built from the caller's pattern with values 1 .. nnz and p's resolved
+// options; checks it against p (INVALID_VALUE: another pattern; NOT_SUPPORTED:
+// merged entries) and leaves the maps in p->upd.  launch_update_values:
+// rewrite p's value arrays from d_val (device, nnz doubles) on p->stream.
+int launch_iota_values(hipStream_t st, double *val, int64_t nnz);  // val[i] = i + 1
+int update_prepare_from_shadow(spmv_plan_s *p, const spmv_plan_s *shadow);
+int launch_update_values(const spmv_plan_s *p, const double *d_val);
 
 }  // namespace spmv

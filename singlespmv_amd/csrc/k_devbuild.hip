@@ -403,13 +403,10 @@ int build_coo_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &) {
 
 
 // ---- layout digest (spmv_plan_digest) ------------------------------------------
-namespace {
-
-struct ArrayRef {
-    const char *name;
-    const void *ptr;
-    int64_t bytes;
-};
+bool is_value_array(const char *name) {
+    const std::string s(name);
+    return s == "val" || s == "ell_val" || s == "ovf_val" || s == "val1";
+}
 
 // the device arrays of a plan with their logical sizes (what the builders
 // write; allocation rounding and per-execute scratch excluded)
@@ -504,6 +501,8 @@ int plan_arrays(const spmv_plan_s *p, std::vector<ArrayRef> &a) {
     return SPMV_ERROR_NOT_SUPPORTED;
 }
 
+namespace {
+
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
@@ -523,15 +522,8 @@ __global__ __launch_bounds__(256) void digest_kernel(const uint32_t *__restrict_
 
 }  // namespace
 
-}  // namespace spmv
-
-using namespace spmv;
-
-extern "C" int spmv_plan_digest(spmv_plan_t p, uint64_t *digests, int32_t cap, int32_t *n_arrays) {
-    SPMV_CHECK_ARG(p != nullptr && n_arrays != nullptr && (cap <= 0 || digests != nullptr), "bad arguments");
-    std::vector<ArrayRef> a;
-    SPMV_RETURN_IF(plan_arrays(p, a));
-    *n_arrays = (int32_t)a.size();
+int plan_digests(const spmv_plan_s *p, const std::vector<ArrayRef> &a, std::vector<uint64_t> &out) {
+    out.assign(a.size(), 0);
     int cur = -1;
     SPMV_HIP_TRY(hipGetDevice(&cur));
     if (cur != p->device) SPMV_HIP_TRY(hipSetDevice(p->device));
@@ -554,7 +546,22 @@ extern "C" int spmv_plan_digest(spmv_plan_t p, uint64_t *digests, int32_t cap, i
         (void)hipGetLastError();
         return SPMV_ERROR_HIP;
     }
-    for (size_t k = 0; k < a.size() && (int32_t)k < cap; ++k) digests[k] = (uint64_t)h[k] ^ (uint64_t)a[k].bytes;
+    for (size_t k = 0; k < a.size(); ++k) out[k] = (uint64_t)h[k] ^ (uint64_t)a[k].bytes;
+    return SPMV_SUCCESS;
+}
+
+}  // namespace spmv
+
+using namespace spmv;
+
+extern "C" int spmv_plan_digest(spmv_plan_t p, uint64_t *digests, int32_t cap, int32_t *n_arrays) {
+    SPMV_CHECK_ARG(p != nullptr && n_arrays != nullptr && (cap <= 0 || digests != nullptr), "bad arguments");
+    std::vector<ArrayRef> a;
+    SPMV_RETURN_IF(plan_arrays(p, a));
+    *n_arrays = (int32_t)a.size();
+    std::vector<uint64_t> d;
+    SPMV_RETURN_IF(plan_digests(p, a, d));
+    for (size_t k = 0; k < a.size() && (int32_t)k < cap; ++k) digests[k] = d[k];
     return SPMV_SUCCESS;
 }
 
