@@ -340,7 +340,11 @@ int spmv_lds_order_probe(int32_t device, int32_t rounds, const int32_t *slot, co
  * spmv_profile, spmv_graph_* and the k = 1, ldx = ldy = 1 case of
  * spmv_execute_multi, which runs the plan's kernels in place on X and Y.
  * n may be anything below 2^31 - 1: an x of 4 GiB and more (n >= 2^29) takes
- * 64-bit offsets in every format (tests/test_gpu_wide_x.py). */
+ * 64-bit offsets in every format (tests/test_gpu_wide_x.py).  m may be
+ * anything below 2^31 - 1 as well: a y of 4 GiB and more (m >= 2^29; for k
+ * right-hand sides m * ldy >= 2^29) and per-row arrays beyond 4 GiB are
+ * addressed in 64 bits in every format, and every execute writes all m
+ * entries of y (tests/test_gpu_tall_y.py). */
 
 /* y = A * x.  x holds n doubles, y holds m doubles. */
 int spmv_execute(spmv_plan_t plan, const double *x, double *y, uint32_t flags);

@@ -485,6 +485,11 @@ __global__ __launch_bounds__(64 * W2) void bin_sum_bin_kernel(
                 sum_mo_tab<U>(TA, sbat(0), lane, mtab);
                 sum_mo_tab<U>(TB, sbat(1), lane, mtab);
                 sum_mo_load<U>(PA, TA, sbat(0), lane, slot2, prod);
+            } else if (R.nb == 1) {
+                // the table the previous bin's loop loaded as this bin's
+                // "batch 1" was its only batch again (clamped); batch 1 is the
+                // next bin's first batch now, and PB is loaded through TB
+                sum_mo_tab<U>(TB, sbat(1), lane, mtab);
             }
             for (int64_t j = 0;; j += 2) {
                 // batch j (PA) is added while j+1's products (table TB) and
