@@ -81,7 +81,8 @@ extern "C" {
  * where the layout is made, not what it is).  The multi-vector entry points
  * (spmv_execute_multi, spmv_time_multi, spmv_multi_path) are new functions
  * and change no struct: the version stays 3.  So do the value-refresh entry
- * points (spmv_plan_update_prepare, spmv_plan_update_values).  Callers may
+ * points (spmv_plan_update_prepare, spmv_plan_update_values) and the BLAS form
+ * (spmv_execute_axpby, spmv_time_axpby, spmv_axpby_path).  Callers may
  * check spmv_api_version() == SPMV_HIP_API_VERSION once at startup; the
  * structs are only ever filled by spmv_options_default / spmv_plan_info of a
  * library with the same version. */
@@ -356,7 +357,7 @@ int spmv_fetch_y(spmv_plan_t plan, double *y_host);
 
 /* y = alpha * A * x (the CSR5 handle's spmv(alpha, y),
  * CSR5_cuda/anonymouslib_cuda.h:262-284); alpha is applied to the finished
- * row sums (one rounded multiply), beta = 0 as everywhere. */
+ * row sums (one rounded multiply), beta = 0 (beta != 0: spmv_execute_axpby). */
 int spmv_execute_alpha(spmv_plan_t plan, double alpha, const double *x, double *y, uint32_t flags);
 
 /* Kernels are launched on this stream (a hipStream_t; NULL = null stream). */
@@ -416,6 +417,57 @@ int spmv_time_multi(spmv_plan_t plan, int32_t k, const double *X_dev, int64_t ld
 int spmv_multi_path(spmv_plan_t plan, int32_t k, const double *X, int64_t ldx,
                     const double *Y, int64_t ldy, uint32_t flags,
                     int32_t *widths, int32_t cap, int32_t *n_blocks);
+
+/* ---- the BLAS form: y = alpha * A * x + beta * y ----------------------------
+ * For every row r: y[r] = dadd_rn(dmul_rn(alpha, s[r]), dmul_rn(beta, y0[r]))
+ * -- two rounded multiplies and one rounded add, never an FMA.  s[r] is, bit
+ * for bit, the row sum spmv_execute gives on this plan (COO: within its
+ * atomics' order); y0 is y on entry.  The non-finite rules of this header's
+ * opening comment hold for s; a non-finite y0[r] with beta != 0 reaches row r
+ * only.  x and y must not overlap.
+ *
+ * beta = 0 (either sign): y0 is never read -- a NaN there does not propagate --
+ * and the call is spmv_execute_alpha: y = dmul_rn(alpha, s), bit for bit.
+ * alpha = 0 is no shortcut: 0 * s is computed, NaN where s is not finite.
+ *
+ * Flags: SPMV_X_DEVICE, SPMV_Y_DEVICE, SPMV_ASYNC and SPMV_X_STAGED as for
+ * spmv_execute.  y is an input: a host y with beta != 0 is uploaded into the
+ * plan's y staging buffer first (H2D of m doubles), then downloaded, and
+ * SPMV_Y_STAGED is refused.  Refusals come before any device work, all
+ * SPMV_ERROR_INVALID_VALUE: a NULL plan; a NULL x or y (with n, m > 0; x may
+ * be NULL with SPMV_X_STAGED); unknown flag bits; SPMV_Y_STAGED; SPMV_X_STAGED
+ * without a staged x.  The call clears the mark spmv_fetch_y needs, like any
+ * other non-staged execute.  The buffer contract above holds: 8-byte
+ * alignment is enough, nothing outside [y, y + m) is read or written, nothing
+ * outside [x, x + n) influences y.
+ *
+ * Paths (spmv_axpby_path).  Fused: the kernels with one writer per row -- CSR
+ * (every kernel), ELL, DIA, and JDS without overflow rows -- apply alpha and
+ * beta in their store epilogue, for one extra 8-byte read per row; the writer
+ * loads y0[r] before it streams the row, with the very indexing its store
+ * uses (DIA: the 16-byte row pair where y is 16-byte aligned).  Generic, every
+ * other plan (SS, COO, CSS, BIN, HYB, JDS with overflow rows): the plan's own
+ * kernels write the row sums into a plan-owned scratch vector (m doubles of
+ * plain device memory, allocated by the first call that needs it and counted
+ * in spmv_plan_info.device_bytes; SPMV_ERROR_OUT_OF_MEMORY leaves the plan
+ * usable and y untouched), then one pass computes y from it.  A plan with
+ * nothing stored (no diagonal, no entry) gives alpha * (+0.0) + beta * y0.
+ *
+ * Not covered: spmv_execute_multi, HIP graphs, spmv_profile, spmv_dist_*, the
+ * drop-in (opt_hip.h) and the CSR5 handle have no alpha / beta form (the
+ * handle keeps spmv_execute_alpha). */
+int spmv_execute_axpby(spmv_plan_t plan, double alpha, const double *x,
+                       double beta, double *y, uint32_t flags);
+
+/* iters back-to-back device-resident axpby executes between two events on the
+ * plan's stream (the axpby counterpart of spmv_time; y is updated in place
+ * iters times). */
+int spmv_time_axpby(spmv_plan_t plan, double alpha, const double *x_dev,
+                    double beta, double *y_dev, int32_t iters, double *ms);
+
+/* *fused = 1: the plan's kernel applies alpha and beta in its store epilogue;
+ * 0: generic path.  A check and a documentation aid, like spmv_multi_path. */
+int spmv_axpby_path(spmv_plan_t plan, int32_t *fused);
 
 /* ---- value refresh: new values on a fixed sparsity pattern -----------------
  * Every layout decision of a plan (the format AUTO picks, slices, bins,

@@ -112,6 +112,7 @@ EXPORTS = [
     "spmv_fetch_y", "spmv_dist_fetch_y", "spmv_plan_built_on_device",
     "spmv_execute_multi", "spmv_time_multi", "spmv_multi_path",
     "spmv_plan_update_prepare", "spmv_plan_update_values",
+    "spmv_execute_axpby", "spmv_time_axpby", "spmv_axpby_path",
 ]
 
 _lib = None
@@ -149,6 +150,9 @@ def lib():
     L.spmv_execute_multi.argtypes = [vp, i32, vp, i64, vp, i64, C.c_uint32]
     L.spmv_time_multi.argtypes = [vp, i32, vp, i64, vp, i64, i32, C.POINTER(f64)]
     L.spmv_multi_path.argtypes = [vp, i32, vp, i64, vp, i64, C.c_uint32, C.POINTER(i32), i32, C.POINTER(i32)]
+    L.spmv_execute_axpby.argtypes = [vp, f64, vp, f64, vp, C.c_uint32]
+    L.spmv_time_axpby.argtypes = [vp, f64, vp, f64, vp, i32, C.POINTER(f64)]
+    L.spmv_axpby_path.argtypes = [vp, C.POINTER(i32)]
     L.spmv_plan_update_prepare.argtypes = [vp, vp, vp, C.c_uint32]
     L.spmv_plan_update_values.argtypes = [vp, vp, C.c_uint32]
     L.spmv_dist_fetch_y.argtypes = [vp, vp]
@@ -577,6 +581,39 @@ class Plan:
         else:
             _check(lib().spmv_execute_alpha(self._h, float(alpha), _ptr(x), _ptr(y), flags),
                    "spmv_execute_alpha")
+
+    def execute_axpby(self, x, y, alpha: float = 1.0, beta: float = 1.0, async_: bool = False) -> None:
+        """y = alpha * A x + beta * y in place (spmv_execute_axpby): two rounded
+        multiplies and one rounded add per row, on the row sums execute()
+        gives.  beta = 0 never reads y.  numpy arrays are host buffers (a host
+        y travels up and down), torch CUDA tensors device buffers; x and y
+        must not overlap."""
+        self._check_xy(x, y)
+        flags = (X_DEVICE if _is_device(x) else 0) | (Y_DEVICE if _is_device(y) else 0)
+        if async_:
+            flags |= ASYNC
+        _check(lib().spmv_execute_axpby(self._h, float(alpha), _ptr(x), float(beta), _ptr(y), flags),
+               "spmv_execute_axpby")
+
+    def time_axpby(self, x_dev, y_dev, alpha: float, beta: float, iters: int) -> float:
+        """Milliseconds for `iters` back-to-back axpby executes (HIP events on
+        the plan's stream); y_dev is updated in place `iters` times."""
+        self._check_xy(x_dev, y_dev)
+        if not (_is_device(x_dev) or self.n == 0) or not (_is_device(y_dev) or self.m == 0):
+            raise ValueError("time_axpby() needs device tensors for x and y")
+        ms = C.c_double()
+        _check(lib().spmv_time_axpby(self._h, float(alpha), _ptr(x_dev), float(beta), _ptr(y_dev), iters,
+                                     C.byref(ms)), "spmv_time_axpby")
+        return ms.value
+
+    def axpby_path(self) -> str:
+        """"fused": the plan's kernel applies alpha and beta in its store
+        epilogue (CSR, ELL, DIA, JDS without overflow rows); "generic": the
+        plan's kernels into a scratch vector, then one axpby pass
+        (spmv_axpby_path)."""
+        fused = C.c_int32()
+        _check(lib().spmv_axpby_path(self._h, C.byref(fused)), "spmv_axpby_path")
+        return "fused" if fused.value else "generic"
 
     def _check_blocks(self, X, Y):
         k, ldx = _check_block(X, self.n, "X", self.device, writable=False)

@@ -741,6 +741,130 @@ int spmv_time_multi(spmv_plan_t p, int32_t k, const double *X_dev, int64_t ldx, 
 
 }  // extern "C"
 
+// ---- y = alpha * A x + beta * y (epilogues: k_csr / k_ell / k_dia.hip; second pass: k_axpby.hip) --
+namespace spmv {
+
+// One writer per row: CSR (every kernel), ELL, DIA, and JDS without overflow
+// rows (its overflow kernel adds into a y the ELL part wrote) take alpha and
+// beta in the store epilogue.  Every other plan runs its own kernels into a
+// scratch vector and one axpby pass.
+static bool axpby_fused(const spmv_plan_s *p) {
+    // probe build: the generic route forced on any plan (tools/axpby_times.py)
+    if (const char *e = probe_env("SPMV_LAUNCH_AXPBY_GENERIC"))
+        if (std::atoi(e) != 0) return false;
+    if (p->format == SPMV_FORMAT_CSR || p->format == SPMV_FORMAT_ELL || p->format == SPMV_FORMAT_DIA) return true;
+    return p->format == SPMV_FORMAT_JDS && p->hyb.nnz == 0 && p->hyb.n_rows == 0;
+}
+
+// the generic path's row sums: m + 2 doubles of plain hipMalloc memory (COO
+// adds into them with f64 atomics), allocated at the first use.  The spare
+// doubles let t start at y's alignment modulo 16 (k_axpby.hip).
+static int axpby_scratch(spmv_plan_s *p) {
+    if (p->ab_scratch) return SPMV_SUCCESS;
+    const size_t keep = p->arena.vmm_min;
+    p->arena.vmm_min = 0;
+    void *q = nullptr;
+    const int st = p->arena.alloc(&q, sizeof(double) * (size_t)(p->m + 2));
+    p->arena.vmm_min = keep;
+    SPMV_RETURN_IF(st);
+    p->ab_scratch = (double *)q;
+    return SPMV_SUCCESS;
+}
+
+// the launches of one axpby execute on device x and y (beta != 0), on p->stream
+static int axpby_dispatch(spmv_plan_s *p, const Axpby &ab, const double *x, double *y) {
+    if (p->m == 0) return SPMV_SUCCESS;
+    if (axpby_fused(p)) {
+        switch (p->format) {
+            case SPMV_FORMAT_CSR: return launch_csr(p, x, y, &ab);
+            case SPMV_FORMAT_DIA: return launch_dia(p, x, y, &ab);
+            default: return launch_ell(p, x, y, &ab);  // ELL, JDS without overflow rows
+        }
+    }
+    SPMV_RETURN_IF(axpby_scratch(p));
+    double *t = p->ab_scratch + ((reinterpret_cast<uintptr_t>(y) >> 3) & 1);
+    SPMV_RETURN_IF(dispatch(p, x, t));
+    return launch_axpby(p, y, t, ab);
+}
+
+}  // namespace spmv
+
+extern "C" {
+
+int spmv_execute_axpby(spmv_plan_t p, double alpha, const double *x, double beta, double *y, uint32_t flags) {
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    const bool staged = (flags & SPMV_X_STAGED) != 0;
+    SPMV_CHECK_ARG((x != nullptr || p->n == 0 || staged) && (y != nullptr || p->m == 0), "x or y is NULL");
+    SPMV_CHECK_ARG(!(flags & ~(SPMV_X_DEVICE | SPMV_Y_DEVICE | SPMV_ASYNC | SPMV_X_STAGED | SPMV_Y_STAGED)),
+                   "spmv_execute_axpby: unknown flag bits");
+    SPMV_CHECK_ARG(!(flags & SPMV_Y_STAGED), "spmv_execute_axpby: SPMV_Y_STAGED is not supported (y is an input)");
+    SPMV_CHECK_ARG(!staged || p->x_stage != nullptr, "SPMV_X_STAGED without a previously staged x");
+    // beta = 0 (either sign): y is never read; alpha * A x as spmv_execute_alpha
+    if (beta == 0.0) return execute_impl(p, alpha, x, y, flags);
+    SPMV_RETURN_IF(bind_device(p));
+    p->y_staged = false;  // like any other non-staged execute (spmv_fetch_y)
+    // every allocation comes first: out of memory leaves y untouched
+    if (!staged && !(flags & SPMV_X_DEVICE) && !p->x_stage) {
+        void *q;
+        SPMV_RETURN_IF(p->arena.alloc(&q, sizeof(double) * (size_t)std::max<int64_t>(p->n, 1)));
+        p->x_stage = (double *)q;
+    }
+    if (!(flags & SPMV_Y_DEVICE) && !p->y_stage) {
+        void *q;
+        SPMV_RETURN_IF(p->arena.alloc(&q, sizeof(double) * (size_t)std::max<int64_t>(p->m, 1)));
+        p->y_stage = (double *)q;
+    }
+    if (p->m && !axpby_fused(p)) SPMV_RETURN_IF(axpby_scratch(p));
+    const double *dx = x;
+    double *dy = y;
+    if (staged) {
+        dx = p->x_stage;
+        flags |= SPMV_X_DEVICE;
+    } else if (!(flags & SPMV_X_DEVICE)) {
+        if (p->n) SPMV_HIP_TRY(hipMemcpyAsync(p->x_stage, x, sizeof(double) * p->n, hipMemcpyHostToDevice, p->stream));
+        dx = p->x_stage;
+    }
+    if (!(flags & SPMV_Y_DEVICE)) {
+        // y is an input: a host y travels up, then down
+        if (p->m) SPMV_HIP_TRY(hipMemcpyAsync(p->y_stage, y, sizeof(double) * p->m, hipMemcpyHostToDevice, p->stream));
+        dy = p->y_stage;
+    }
+    const Axpby ab{alpha, beta};
+    SPMV_RETURN_IF(axpby_dispatch(p, ab, dx, dy));
+    if (!(flags & SPMV_Y_DEVICE)) {
+        if (p->m) SPMV_HIP_TRY(hipMemcpyAsync(y, dy, sizeof(double) * p->m, hipMemcpyDeviceToHost, p->stream));
+        SPMV_HIP_TRY(hipStreamSynchronize(p->stream));
+    } else if (!(flags & SPMV_ASYNC) || !(flags & SPMV_X_DEVICE)) {
+        SPMV_HIP_TRY(hipStreamSynchronize(p->stream));
+    }
+    return SPMV_SUCCESS;
+}
+
+int spmv_time_axpby(spmv_plan_t p, double alpha, const double *x_dev, double beta, double *y_dev, int32_t iters,
+                    double *ms) {
+    SPMV_CHECK_ARG(p != nullptr && ms != nullptr && iters > 0, "bad arguments");
+    SPMV_CHECK_ARG((x_dev != nullptr || p->n == 0) && (y_dev != nullptr || p->m == 0), "x or y is NULL");
+    SPMV_RETURN_IF(bind_device(p));
+    p->y_staged = false;
+    if (beta == 0.0)
+        return time_on_stream(p->stream, iters, ms, [&]() -> int {
+            SPMV_RETURN_IF(dispatch(p, x_dev, y_dev));
+            return launch_scale(p, y_dev, alpha);
+        });
+    if (p->m && !axpby_fused(p)) SPMV_RETURN_IF(axpby_scratch(p));
+    const Axpby ab{alpha, beta};
+    return time_on_stream(p->stream, iters, ms, [&] { return axpby_dispatch(p, ab, x_dev, y_dev); });
+}
+
+int spmv_axpby_path(spmv_plan_t p, int32_t *fused) {
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    SPMV_CHECK_ARG(fused != nullptr, "fused out-pointer is NULL");
+    *fused = axpby_fused(p) ? 1 : 0;
+    return SPMV_SUCCESS;
+}
+
+}  // extern "C"
+
 // ---- value refresh (new values on the plan's pattern; kernels: k_update.hip) --
 extern "C" {
 

@@ -71,6 +71,12 @@ __device__ __forceinline__ double madd(double a, double b, double c) {
     return __dadd_rn(c, __dmul_rn(a, b));
 }
 
+// The store epilogue of spmv_execute_axpby: alpha * s + beta * y0 as two
+// rounded multiplies and one rounded add, never an FMA.
+__device__ __forceinline__ double axpby(double alpha, double s, double beta, double y0) {
+    return __dadd_rn(__dmul_rn(alpha, s), __dmul_rn(beta, y0));
+}
+
 // Sum over aligned groups of G lanes (G power of two <= 64); every lane of a
 // group ends with the group total.  Butterfly order is fixed -> deterministic.
 template <int G>

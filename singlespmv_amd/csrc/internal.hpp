@@ -470,6 +470,9 @@ struct spmv_plan_s {
     double *mx_stage = nullptr, *my_stage = nullptr;
     int64_t mx_cap = 0, my_cap = 0;  // doubles
     double *m_scratch = nullptr;
+    // spmv_execute_axpby, generic path: the row sums t = A x (m doubles, plain
+    // hipMalloc: COO adds into it with f64 atomics), allocated at the first use
+    double *ab_scratch = nullptr;
     int64_t stored_slots = 0;
     int64_t empty_rows = 0;
     int64_t algo_bytes = 0;
@@ -630,12 +633,22 @@ inline void phase_mark(const spmv_plan_s *p) {
     if (p->prof_k >= 0 && p->prof_k < 7) (void)hipEventRecord(p->prof_ev[++p->prof_k], p->stream);
 }
 
-// kernels -- launch y = A x on p->stream (device x, y).
-int launch_csr(const spmv_plan_s *p, const double *x, double *y);
-int launch_ell(const spmv_plan_s *p, const double *x, double *y);
+// spmv_execute_axpby's scalars (beta != 0: beta = 0 is spmv_execute_alpha)
+struct Axpby {
+    double alpha, beta;
+};
+
+// kernels -- launch y = A x on p->stream (device x, y).  CSR, ELL (the sliced
+// ELL part of JDS included) and DIA take an optional Axpby: the same launch
+// with y = alpha * A x + beta * y in the store epilogue (one writer per row).
+int launch_csr(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab = nullptr);
+int launch_ell(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab = nullptr);
 int launch_hyb_overflow(const spmv_plan_s *p, const double *x, double *y);
 int launch_ss(const spmv_plan_s *p, const double *x, double *y);
-int launch_dia(const spmv_plan_s *p, const double *x, double *y);
+int launch_dia(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab = nullptr);
+// k_axpby.hip -- y = alpha * t + beta * y over m rows on p->stream, the second
+// pass of the generic axpby path (t = nullptr: every t[r] is +0.0)
+int launch_axpby(const spmv_plan_s *p, double *y, const double *t, const Axpby &ab);
 int launch_css(const spmv_plan_s *p, const double *x, double *y);
 int launch_coo(const spmv_plan_s *p, const double *x, double *y);
 int launch_bin(const spmv_plan_s *p, const double *x, double *y);

@@ -25,6 +25,10 @@
 //   csr_adaptive   skewed rows binned by length, all bins in one launch, a
 //                  row per L-lane group or per workgroup (config 3; its ADD
 //                  instance finishes the HYB / JDS overflow rows)
+// Each has an *_axpby_kernel twin (spmv_execute_axpby: y = alpha A x + beta y
+// in the store epilogue, csr_slab_store<AB> / csr_store_row<ADD, AB>; the
+// row's writer loads its y0 before the row is streamed); alpha and beta are
+// arguments of the twins only.
 // csr_vec4<L> (a row per group, no slabs: the round-3 kernel) is compiled
 // into the probe build only, for A/Bs (SPMV_LAUNCH_CSR=0).
 //
@@ -75,13 +79,18 @@ __device__ __forceinline__ double csr_row_sum(int64_t s, int64_t e, int lane, co
 }
 
 // ADD: y[yrow[row]] += sum (the HYB/JDS overflow, one writer per row);
-// otherwise y[row] = sum
-template <bool ADD>
+// AB (spmv_execute_axpby): y[row] = alpha * sum + beta * y0, y0 = the y[row]
+// the row's writer loaded before its walk (device.hpp axpby); otherwise
+// y[row] = sum
+template <bool ADD, bool AB = false>
 __device__ __forceinline__ void csr_store_row(double *__restrict__ y, const int32_t *__restrict__ yrow, int64_t row,
-                                              double sum) {
+                                              double sum, double alpha = 0.0, double beta = 0.0, double y0 = 0.0) {
+    static_assert(!(ADD && AB), "the overflow add has no axpby form");
     if (ADD) {
         const int64_t yi = yrow[row];
         y[yi] = __dadd_rn(y[yi], sum);
+    } else if (AB) {
+        y[row] = axpby(alpha, sum, beta, y0);
     } else {
         y[row] = sum;
     }
@@ -248,13 +257,24 @@ __device__ __forceinline__ void csr_batch_sum(const CsrBatch<L, U> &B, const Csr
 }
 
 // the wave's 64 row sums, written by its group leaders, leave LDS in one
-// coalesced store
-__device__ __forceinline__ void csr_slab_store(const double *ys, double *__restrict__ y, int64_t r0, int64_t m) {
+// coalesced store.  AB (spmv_execute_axpby): lane t stores alpha * sum + beta *
+// y0, y0 = the y[r0 + t] it loaded before the slab's batches (csr_slab_y0).
+template <bool AB = false>
+__device__ __forceinline__ void csr_slab_store(const double *ys, double *__restrict__ y, int64_t r0, int64_t m,
+                                               double alpha = 0.0, double beta = 0.0, double y0 = 0.0) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     const int lane = threadIdx.x & 63;
-    if (r0 + lane < m) __builtin_nontemporal_store(ys[lane], y + r0 + lane);
+    if (r0 + lane < m) {
+        if constexpr (AB) __builtin_nontemporal_store(axpby(alpha, ys[lane], beta, y0), y + r0 + lane);
+        else __builtin_nontemporal_store(ys[lane], y + r0 + lane);
+    }
+}
+// lane t's y0 of the slab at r0: indexed exactly as csr_slab_store's store
+__device__ __forceinline__ double csr_slab_y0(const double *__restrict__ y, int64_t r0, int64_t m) {
+    const int lane = threadIdx.x & 63;
+    return r0 + lane < m ? ld_stream(y + r0 + lane) : 0.0;
 }
 
 // csr_slab2<L, U, O32>: one wave per slab; each batch is loaded, gathered
@@ -283,6 +303,36 @@ __global__ __launch_bounds__(256) void csr_slab2_kernel(int64_t m, const RP *__r
     csr_slab_store(ysl[wv], y, r0, m);
 }
 
+// y = alpha * A x + beta * y: csr_slab2's frame around the same batches, with
+// lane t's y0 loaded ahead of them and the axpby store.  (A frame of its own,
+// not a shared body function: csr_slab2_kernel's code stays what it was --
+// hoisting its frame into a function moved its instructions.)
+template <int L, typename RP, int U, bool O32>
+__global__ __launch_bounds__(256) void csr_slab2_axpby_kernel(int64_t m, const RP *__restrict__ rp,
+                                                              const int32_t *__restrict__ col,
+                                                              const double *__restrict__ val,
+                                                              const double *__restrict__ x, double *__restrict__ y,
+                                                              bool vh, double alpha, double beta) {
+    __shared__ double ysl[4][64];
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform (SGPR)
+    const int lane = threadIdx.x & 63;
+    const int64_t r0 = ((int64_t)blockIdx.x * 4 + wv) * 64;
+    if (r0 >= m) return;  // wave-uniform
+    const int64_t rl = r0 + lane;
+    const int64_t base = (int64_t)rp[r0] & ~(int64_t)3;
+    const int rpl = (int)((int64_t)rp[rl < m ? rl : m] - base);
+    const int rpe = (int)((int64_t)rp[r0 + 64 < m ? r0 + 64 : m] - base);
+    const double y0 = csr_slab_y0(y, r0, m);
+    const CsrStream<O32> A(col, val, base, vh);
+    auto xg = [&](int c) -> double { return *(const double *)at_bytes<O32>(x, c, 8); };
+    for (int st = 0; st < L; st += U) {
+        CsrBatch<L, U> B;
+        csr_batch_load(B, A, rpl, rpe, st);
+        csr_batch_sum(B, A, xg, ysl[wv], st);
+    }
+    csr_slab_store<true>(ysl[wv], y, r0, m, alpha, beta, y0);
+}
+
 // csr_slabx<L, U, S, O32>: csr_slab2 for matrices whose rows stay near the
 // diagonal (banded, config 4).  A workgroup owns 256 S consecutive rows (each
 // wave S consecutive 64-row slabs) and reads x over one column window
@@ -295,11 +345,12 @@ __global__ __launch_bounds__(256) void csr_slab2_kernel(int64_t m, const RP *__r
 // issued before the window is staged.  Lanes whose loaded entry lies
 // outside the window (masked entries of a neighbouring row) read a clamped,
 // in-window slot.
-template <int L, typename RP, int U, int S, bool O32>
+template <int L, typename RP, int U, int S, bool O32, bool AB = false>
 __device__ __forceinline__ void csr_slabx_body(int64_t m, const RP *__restrict__ rp, const int32_t *__restrict__ col,
                                                const double *__restrict__ val, const double *__restrict__ x,
                                                double *__restrict__ y, const int32_t *__restrict__ win0, int32_t win,
-                                               int64_t n, bool vh, double *xs, double (*ysl)[64]) {
+                                               int64_t n, bool vh, double *xs, double (*ysl)[64],
+                                               double alpha = 0.0, double beta = 0.0) {
     constexpr int NB = L / U;   // batches per slab
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -314,6 +365,12 @@ __device__ __forceinline__ void csr_slabx_body(int64_t m, const RP *__restrict__
         const int64_t rk = r0 + 64 * k + lane, ek = r0 + 64 * (k + 1);
         rpl[k] = (int)((int64_t)rp[rk < m ? rk : m] - base);
         rpe[k] = (int)((int64_t)rp[ek < m ? ek : m] - base);
+    }
+    double y0[S];  // AB: lane t's y of each slab, loaded ahead of the stream
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        y0[k] = 0.0;
+        if constexpr (AB) y0[k] = csr_slab_y0(y, r0 + 64 * k, m);
     }
     const CsrStream<O32> A(col, val, base, vh);
     auto load = [&](CsrBatch<L, U> &B, int i) {  // batch i: slab i / NB, steps (i % NB) U ..
@@ -337,7 +394,10 @@ __device__ __forceinline__ void csr_slabx_body(int64_t m, const RP *__restrict__
     auto compute = [&](const CsrBatch<L, U> &B, int i) {
         csr_batch_sum(B, A, xw, ysl[wv], (i % NB) * U);
         if (i % NB == NB - 1) {  // the slab is done; ysl[wv] is free again after the store
-            csr_slab_store(ysl[wv], y, r0 + 64 * (i / NB), m);
+            double y0k = y0[0];
+#pragma unroll
+            for (int k = 1; k < S; ++k) y0k = i / NB == k ? y0[k] : y0k;
+            csr_slab_store<AB>(ysl[wv], y, r0 + 64 * (i / NB), m, alpha, beta, y0k);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -384,6 +444,19 @@ __global__ __launch_bounds__(256) void csr_slabx_kernel(int64_t m, const RP *__r
     csr_slabx_body<L, RP, U, S, O32>(m, rp, col, val, x, y, win0, win, n, vh, xs, ysl);
 }
 
+// y = alpha * A x + beta * y: the same body with the axpby epilogue
+template <int L, typename RP, int U, int S, bool O32>
+__global__ __launch_bounds__(256) void csr_slabx_axpby_kernel(int64_t m, const RP *__restrict__ rp,
+                                                              const int32_t *__restrict__ col,
+                                                              const double *__restrict__ val,
+                                                              const double *__restrict__ x, double *__restrict__ y,
+                                                              const int32_t *__restrict__ win0, int32_t win,
+                                                              int64_t n, bool vh, double alpha, double beta) {
+    extern __shared__ double xs[];  // [win]
+    __shared__ double ysl[4][64];
+    csr_slabx_body<L, RP, U, S, O32, true>(m, rp, col, val, x, y, win0, win, n, vh, xs, ysl, alpha, beta);
+}
+
 // Adaptive CSR in ONE launch: workgroup ranges map to the length bins
 // (blk_off), so all bins run concurrently instead of back to back; the bin
 // test is workgroup-uniform (no divergence).  Bin b has L = kCsrBinLanes[b]
@@ -396,26 +469,30 @@ struct CsrBinTable {
 // the short-row bins fill in behind them instead of forming the tail
 constexpr int kCsrLaunchOrder[kCsrBins] = {7, 6, 5, 4, 3, 2, 1, 0};
 
-template <int L, typename RP, bool ADD>
+template <int L, typename RP, bool ADD, bool AB>
 __device__ __forceinline__ void csr_rows_body(int64_t wg, int64_t nrows, const int32_t *__restrict__ rows,
                                               const RP *__restrict__ rp, const int32_t *__restrict__ col,
                                               const double *__restrict__ val, const double *__restrict__ x,
-                                              double *__restrict__ y, const int32_t *__restrict__ yrow) {
+                                              double *__restrict__ y, const int32_t *__restrict__ yrow, double alpha,
+                                              double beta) {
     const int64_t g = (wg * 256 + threadIdx.x) / L;
     const int lane = threadIdx.x & (L - 1);
     if (g >= nrows) return;
     const int64_t row = rows[g];
+    double y0 = 0.0;  // AB: the writer's y[row], loaded before the row's walk
+    if constexpr (AB) {
+        if (lane == 0) y0 = ld_stream(y + row);
+    }
     const double acc = group_sum<L>(csr_row_sum<L>(rp[row], rp[row + 1], lane, col, val, x, false));
-    if (lane == 0) csr_store_row<ADD>(y, yrow, row, acc);
+    if (lane == 0) csr_store_row<ADD, AB>(y, yrow, row, acc, alpha, beta, y0);
 }
 
-template <typename RP, bool ADD>
-__global__ __launch_bounds__(256) void csr_adaptive_kernel(CsrBinTable t, const int32_t *__restrict__ rows,
-                                                           const RP *__restrict__ rp,
-                                                           const int32_t *__restrict__ col,
-                                                           const double *__restrict__ val,
-                                                           const double *__restrict__ x, double *__restrict__ y,
-                                                           const int32_t *__restrict__ yrow) {
+template <typename RP, bool ADD, bool AB>
+__device__ __forceinline__ void csr_adaptive_body(const CsrBinTable &t, const int32_t *__restrict__ rows,
+                                                  const RP *__restrict__ rp, const int32_t *__restrict__ col,
+                                                  const double *__restrict__ val, const double *__restrict__ x,
+                                                  double *__restrict__ y, const int32_t *__restrict__ yrow,
+                                                  double alpha, double beta) {
     __shared__ double part[4];
     const int64_t blk = blockIdx.x;
     int k = 0;
@@ -425,31 +502,58 @@ __global__ __launch_bounds__(256) void csr_adaptive_kernel(CsrBinTable t, const 
     const int32_t *br = rows + t.row_off[b];
     const int64_t n = t.row_off[b + 1] - t.row_off[b];
     switch (b) {
-        case 0: csr_rows_body<1, RP, ADD>(wg, n, br, rp, col, val, x, y, yrow); break;
-        case 1: csr_rows_body<2, RP, ADD>(wg, n, br, rp, col, val, x, y, yrow); break;
-        case 2: csr_rows_body<4, RP, ADD>(wg, n, br, rp, col, val, x, y, yrow); break;
-        case 3: csr_rows_body<8, RP, ADD>(wg, n, br, rp, col, val, x, y, yrow); break;
-        case 4: csr_rows_body<16, RP, ADD>(wg, n, br, rp, col, val, x, y, yrow); break;
-        case 5: csr_rows_body<32, RP, ADD>(wg, n, br, rp, col, val, x, y, yrow); break;
-        case 6: csr_rows_body<64, RP, ADD>(wg, n, br, rp, col, val, x, y, yrow); break;
+        case 0: csr_rows_body<1, RP, ADD, AB>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta); break;
+        case 1: csr_rows_body<2, RP, ADD, AB>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta); break;
+        case 2: csr_rows_body<4, RP, ADD, AB>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta); break;
+        case 3: csr_rows_body<8, RP, ADD, AB>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta); break;
+        case 4: csr_rows_body<16, RP, ADD, AB>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta); break;
+        case 5: csr_rows_body<32, RP, ADD, AB>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta); break;
+        case 6: csr_rows_body<64, RP, ADD, AB>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta); break;
         default: {
             // one workgroup per row: four wave sums added in wave order
             const int64_t row = br[wg];
+            double y0 = 0.0;
+            if constexpr (AB) {
+                if (threadIdx.x == 0) y0 = ld_stream(y + row);
+            }
             const double acc =
                 group_sum<64>(csr_row_sum<256>(rp[row], rp[row + 1], (int)threadIdx.x, col, val, x, false));
             if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
             __syncthreads();
             if (threadIdx.x == 0)
-                csr_store_row<ADD>(y, yrow, row, __dadd_rn(__dadd_rn(part[0], part[1]), __dadd_rn(part[2], part[3])));
+                csr_store_row<ADD, AB>(y, yrow, row,
+                                       __dadd_rn(__dadd_rn(part[0], part[1]), __dadd_rn(part[2], part[3])), alpha,
+                                       beta, y0);
         }
     }
+}
+
+template <typename RP, bool ADD>
+__global__ __launch_bounds__(256) void csr_adaptive_kernel(CsrBinTable t, const int32_t *__restrict__ rows,
+                                                           const RP *__restrict__ rp,
+                                                           const int32_t *__restrict__ col,
+                                                           const double *__restrict__ val,
+                                                           const double *__restrict__ x, double *__restrict__ y,
+                                                           const int32_t *__restrict__ yrow) {
+    csr_adaptive_body<RP, ADD, false>(t, rows, rp, col, val, x, y, yrow, 0.0, 0.0);
+}
+
+// y = alpha * A x + beta * y: the same body with the axpby epilogue
+template <typename RP>
+__global__ __launch_bounds__(256) void csr_adaptive_axpby_kernel(CsrBinTable t, const int32_t *__restrict__ rows,
+                                                                 const RP *__restrict__ rp,
+                                                                 const int32_t *__restrict__ col,
+                                                                 const double *__restrict__ val,
+                                                                 const double *__restrict__ x, double *__restrict__ y,
+                                                                 double alpha, double beta) {
+    csr_adaptive_body<RP, false, true>(t, rows, rp, col, val, x, y, nullptr, alpha, beta);
 }
 
 // one launch of the adaptive kernel over length bins (bin_off: host offsets)
 template <typename RP, bool ADD>
 static int launch_adaptive(const spmv_plan_s *p, const int64_t *bin_off, const int32_t *bin_rows, const RP *rp,
                            const int32_t *col, const double *val, const double *x, double *y,
-                           const int32_t *yrow) {
+                           const int32_t *yrow, const Axpby *ab = nullptr) {
     CsrBinTable t;
     t.blk_off[0] = 0;
     for (int b = 0; b <= kCsrBins; ++b) t.row_off[b] = bin_off[b];
@@ -460,6 +564,14 @@ static int launch_adaptive(const spmv_plan_s *p, const int64_t *bin_off, const i
         t.blk_off[k + 1] = t.blk_off[k] + (L >= 256 ? n : (n * L + 255) / 256);
     }
     if (t.blk_off[kCsrBins] == 0) return SPMV_SUCCESS;
+    if constexpr (!ADD) {
+        if (ab) {
+            hipLaunchKernelGGL((csr_adaptive_axpby_kernel<RP>), dim3((unsigned)t.blk_off[kCsrBins]), dim3(256), 0,
+                               p->stream, t, bin_rows, rp, col, val, x, y, ab->alpha, ab->beta);
+            SPMV_HIP_TRY(hipGetLastError());
+            return SPMV_SUCCESS;
+        }
+    }
     hipLaunchKernelGGL((csr_adaptive_kernel<RP, ADD>), dim3((unsigned)t.blk_off[kCsrBins]), dim3(256), 0, p->stream,
                        t, bin_rows, rp, col, val, x, y, yrow);
     SPMV_HIP_TRY(hipGetLastError());
@@ -493,7 +605,7 @@ static CsrLaunch csr_launch_shape() {
 #endif
 
 template <int L, typename RP, int U>
-static void launch_slab_u(const spmv_plan_s *p, int kind, size_t lds, const double *x, double *y) {
+static void launch_slab_u(const spmv_plan_s *p, int kind, size_t lds, const double *x, double *y, const Axpby *ab) {
     constexpr int UU = U < L ? U : L;
     const int64_t waves = (p->m + 63) / 64;
     const CsrDev &c = p->csr;
@@ -508,17 +620,22 @@ static void launch_slab_u(const spmv_plan_s *p, int kind, size_t lds, const doub
         const int32_t win = c.win_s[csr_win_index(S)];
         const size_t wl = std::max(lds, sizeof(double) * (size_t)win);
         const unsigned grid = (unsigned)((p->m + 256 * S - 1) / (256 * S));
-        auto go = [&](auto kern) {
+        auto go = [&](auto kern, auto... ab_args) {
             hipLaunchKernelGGL(kern, dim3(grid), dim3(256), wl, p->stream, p->m, (const RP *)c.row_ptr, c.col, c.val,
-                               x, y, c.win0, win, p->n, c.val_halves);
+                               x, y, c.win0, win, p->n, c.val_halves, ab_args...);
         };
         // 32-bit offsets span the wave's S slabs (off32 is per single slab)
         auto go_s = [&](auto sc) {
             constexpr int SS = decltype(sc)::value;
-            if (c.off32 && (SS == 1 || (int64_t)SS * c.slab_max + 512 < ((int64_t)1 << 28)))
+            const bool o32 = c.off32 && (SS == 1 || (int64_t)SS * c.slab_max + 512 < ((int64_t)1 << 28));
+            if (ab) {
+                if (o32) go(csr_slabx_axpby_kernel<L, RP, UU, SS, true>, ab->alpha, ab->beta);
+                else go(csr_slabx_axpby_kernel<L, RP, UU, SS, false>, ab->alpha, ab->beta);
+            } else if (o32) {
                 go(csr_slabx_kernel<L, RP, UU, SS, true>);
-            else
+            } else {
                 go(csr_slabx_kernel<L, RP, UU, SS, false>);
+            }
         };
 #ifdef SPMV_PROBES
         if (S == 1) go_s(std::integral_constant<int, 1>{});
@@ -529,30 +646,36 @@ static void launch_slab_u(const spmv_plan_s *p, int kind, size_t lds, const doub
 #endif
         return;
     }
-    auto go = [&](auto kern) {
+    auto go = [&](auto kern, auto... ab_args) {
         hipLaunchKernelGGL(kern, dim3((unsigned)((waves + 3) / 4)), dim3(256), lds, p->stream, p->m,
-                           (const RP *)c.row_ptr, c.col, c.val, x, y, c.val_halves);
+                           (const RP *)c.row_ptr, c.col, c.val, x, y, c.val_halves, ab_args...);
     };
-    if (c.off32) go(csr_slab2_kernel<L, RP, UU, true>);
-    else go(csr_slab2_kernel<L, RP, UU, false>);
+    if (ab) {
+        if (c.off32) go(csr_slab2_axpby_kernel<L, RP, UU, true>, ab->alpha, ab->beta);
+        else go(csr_slab2_axpby_kernel<L, RP, UU, false>, ab->alpha, ab->beta);
+    } else if (c.off32) {
+        go(csr_slab2_kernel<L, RP, UU, true>);
+    } else {
+        go(csr_slab2_kernel<L, RP, UU, false>);
+    }
 }
 
 // The product instantiates only the default shape (CsrLaunch{}: slab 3, U =
 // 4, S = kCsrSlabsPerWave); the probe build adds csr_vec4 and U / S / LDS
 // variants, read at every launch.
 template <int L, typename RP>
-static int launch_csr_t(const spmv_plan_s *p, int64_t nrows, const double *x, double *y) {
+static int launch_csr_t(const spmv_plan_s *p, int64_t nrows, const double *x, double *y, const Axpby *ab) {
     const int64_t threads = nrows * L;
     const int64_t blocks = (threads + 255) / 256;
     if (blocks == 0) return SPMV_SUCCESS;
 #ifdef SPMV_PROBES
-    const CsrLaunch sh = csr_launch_shape();
+    const CsrLaunch sh = ab ? CsrLaunch{} : csr_launch_shape();  // the axpby epilogue: the product's shape only
     if (sh.slab) {
         switch (sh.u) {
-            case 1: launch_slab_u<L, RP, 1>(p, sh.slab, sh.lds, x, y); break;
-            case 2: launch_slab_u<L, RP, 2>(p, sh.slab, sh.lds, x, y); break;
-            case 8: launch_slab_u<L, RP, 8>(p, sh.slab, sh.lds, x, y); break;
-            default: launch_slab_u<L, RP, 4>(p, sh.slab, sh.lds, x, y);
+            case 1: launch_slab_u<L, RP, 1>(p, sh.slab, sh.lds, x, y, nullptr); break;
+            case 2: launch_slab_u<L, RP, 2>(p, sh.slab, sh.lds, x, y, nullptr); break;
+            case 8: launch_slab_u<L, RP, 8>(p, sh.slab, sh.lds, x, y, nullptr); break;
+            default: launch_slab_u<L, RP, 4>(p, sh.slab, sh.lds, x, y, ab);
         }
     } else {
         hipLaunchKernelGGL((csr_vec4_kernel<L, RP>), dim3((unsigned)blocks), dim3(256), sh.lds, p->stream, nrows,
@@ -560,40 +683,43 @@ static int launch_csr_t(const spmv_plan_s *p, int64_t nrows, const double *x, do
     }
 #else
     constexpr CsrLaunch sh{};
-    launch_slab_u<L, RP, sh.u>(p, sh.slab, sh.lds, x, y);
+    launch_slab_u<L, RP, sh.u>(p, sh.slab, sh.lds, x, y, ab);
 #endif
     SPMV_HIP_TRY(hipGetLastError());
     return SPMV_SUCCESS;
 }
 
 template <typename RP>
-static int launch_csr_lanes(const spmv_plan_s *p, int lanes, int64_t nrows, const double *x, double *y) {
+static int launch_csr_lanes(const spmv_plan_s *p, int lanes, int64_t nrows, const double *x, double *y,
+                            const Axpby *ab) {
     switch (lanes) {
-        case 1: return launch_csr_t<1, RP>(p, nrows, x, y);
-        case 2: return launch_csr_t<2, RP>(p, nrows, x, y);
-        case 4: return launch_csr_t<4, RP>(p, nrows, x, y);
-        case 8: return launch_csr_t<8, RP>(p, nrows, x, y);
-        case 16: return launch_csr_t<16, RP>(p, nrows, x, y);
-        case 32: return launch_csr_t<32, RP>(p, nrows, x, y);
-        case 64: return launch_csr_t<64, RP>(p, nrows, x, y);
+        case 1: return launch_csr_t<1, RP>(p, nrows, x, y, ab);
+        case 2: return launch_csr_t<2, RP>(p, nrows, x, y, ab);
+        case 4: return launch_csr_t<4, RP>(p, nrows, x, y, ab);
+        case 8: return launch_csr_t<8, RP>(p, nrows, x, y, ab);
+        case 16: return launch_csr_t<16, RP>(p, nrows, x, y, ab);
+        case 32: return launch_csr_t<32, RP>(p, nrows, x, y, ab);
+        case 64: return launch_csr_t<64, RP>(p, nrows, x, y, ab);
         default: set_error("csr lanes must be a power of two in [1,64]"); return SPMV_ERROR_INVALID_VALUE;
     }
 }
 
 template <typename RP>
-static int launch_csr_rp(const spmv_plan_s *p, const double *x, double *y) {
+static int launch_csr_rp(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab) {
     const CsrDev &c = p->csr;
-    if (!c.bin_rows) return launch_csr_lanes<RP>(p, c.lanes, p->m, x, y);
+    if (!c.bin_rows) return launch_csr_lanes<RP>(p, c.lanes, p->m, x, y, ab);
     // adaptive: every bin in one launch (workgroup ranges per bin)
-    return launch_adaptive<RP, false>(p, c.bin_off, c.bin_rows, (const RP *)c.row_ptr, c.col, c.val, x, y, nullptr);
+    return launch_adaptive<RP, false>(p, c.bin_off, c.bin_rows, (const RP *)c.row_ptr, c.col, c.val, x, y, nullptr,
+                                      ab);
 }
 
-int launch_csr(const spmv_plan_s *p, const double *x, double *y) {
+int launch_csr(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab) {
     if (p->nnz == 0) {  // no entries: y = 0 without touching x (x may be NULL when n == 0)
+        if (p->m && ab) return launch_axpby(p, y, nullptr, *ab);  // alpha * (+0.0) + beta * y
         if (p->m) SPMV_HIP_TRY(hipMemsetAsync(y, 0, sizeof(double) * (size_t)p->m, p->stream));
         return SPMV_SUCCESS;
     }
-    return p->csr.rp64 ? launch_csr_rp<int64_t>(p, x, y) : launch_csr_rp<int32_t>(p, x, y);
+    return p->csr.rp64 ? launch_csr_rp<int64_t>(p, x, y, ab) : launch_csr_rp<int32_t>(p, x, y, ab);
 }
 
 // HYB / JDS overflow: the adaptive kernel over the overflow rows binned by

@@ -48,11 +48,18 @@ namespace spmv {
 // 16 / K rows x K planes, ds_write_b64) hit 16 different bank pairs.
 //
 // K = 1 is the single-vector kernel: ldx = ldy = 1, and YMODE is its store.
-template <int K, int UNROLL, bool LDSX, int YMODE>
+//
+// AB (K = 1, spmv_execute_axpby): the store writes alpha * sum + beta * y0
+// (device.hpp axpby).  y0 is read with the very access the store uses -- the
+// 16-byte row pair where y is 16-byte aligned, else two scalars -- and its
+// load is issued before the diagonal loop, so it never trails the wave.
+template <int K, int UNROLL, bool LDSX, int YMODE, bool AB = false>
 __device__ __forceinline__ void dia_body(int64_t m, int64_t mp, int64_t n, int n_diags,
                                          const int32_t *__restrict__ off, int32_t off_min, int32_t win, int32_t wpad,
                                          const double *__restrict__ val, const double *__restrict__ X, int64_t ldx,
-                                         double *__restrict__ Y, int64_t ldy, int32_t group, double *xs) {
+                                         double *__restrict__ Y, int64_t ldy, int32_t group, double *xs,
+                                         double alpha = 0.0, double beta = 0.0) {
+    static_assert(!AB || K == 1, "the axpby epilogue is single-vector");
     const int64_t r0 = 2 * (int64_t)blockIdx.x * blockDim.x;
     const int64_t r = r0 + 2 * threadIdx.x;
     // group > 0 (DiaDev::group): blocks interleaved per group of `group`
@@ -77,6 +84,15 @@ __device__ __forceinline__ void dia_body(int64_t m, int64_t mp, int64_t n, int n
         __syncthreads();
     }
     if (r >= m) return;
+    f64x2 y0 = {0.0, 0.0};
+    if constexpr (AB) {  // the store's own branches, below
+        if (r + 1 < m && (reinterpret_cast<uintptr_t>(Y) & 15) == 0) {
+            y0 = ld_stream2(Y + r);
+        } else {
+            y0.x = ld_stream(Y + r);
+            if (r + 1 < m) y0.y = ld_stream(Y + r + 1);
+        }
+    }
     double a0[K], a1[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) a0[j] = a1[j] = 0.0;
@@ -131,6 +147,10 @@ __device__ __forceinline__ void dia_body(int64_t m, int64_t mp, int64_t n, int n
     }
     for (; d < n_diags; ++d) step(ld_stream2(vb + (int64_t)d * dstride), off[d]);
     if constexpr (K == 1) {
+        if constexpr (AB) {
+            a0[0] = axpby(alpha, a0[0], beta, y0.x);
+            a1[0] = axpby(alpha, a1[0], beta, y0.y);
+        }
         // y is written once and not re-read: the row pair as one 16-byte
         // nontemporal store where y is 16-byte aligned (r is even)
         if (r + 1 < m && (reinterpret_cast<uintptr_t>(Y) & 15) == 0) {
@@ -159,6 +179,18 @@ __global__ __launch_bounds__(256) void dia_kernel(int64_t m, int64_t mp, int64_t
                                                   double *__restrict__ y, int32_t group) {
     extern __shared__ double xs[];
     dia_body<1, UNROLL, LDSX, YMODE>(m, mp, n, n_diags, off, off_min, win, 0, val, x, 1, y, 1, group, xs);
+}
+
+// y = alpha * A x + beta * y: the single-vector body with the axpby epilogue
+template <bool LDSX>
+__global__ __launch_bounds__(256) void dia_axpby_kernel(int64_t m, int64_t mp, int64_t n, int n_diags,
+                                                        const int32_t *__restrict__ off, int32_t off_min, int32_t win,
+                                                        const double *__restrict__ val,
+                                                        const double *__restrict__ x,
+                                                        double *__restrict__ y, int32_t group, double alpha,
+                                                        double beta) {
+    extern __shared__ double xs[];
+    dia_body<1, 8, LDSX, 0, true>(m, mp, n, n_diags, off, off_min, win, 0, val, x, 1, y, 1, group, xs, alpha, beta);
 }
 
 template <int K, bool LDSX>
@@ -190,10 +222,11 @@ static DiaGeom dia_geom(const spmv_plan_s *p) {
     return {dim3((unsigned)(((p->m + 1) / 2 + 255) / 256)), off_min, 512 + (int64_t)off_max - off_min + 1};
 }
 
-int launch_dia(const spmv_plan_s *p, const double *x, double *y) {
+int launch_dia(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab) {
     const DiaDev &d = p->dia;
     if (p->m == 0) return SPMV_SUCCESS;
-    if (d.n_diags == 0) {  // no stored diagonal: y = 0
+    if (d.n_diags == 0) {  // no stored diagonal: y = 0 (axpby: alpha * (+0.0) + beta * y)
+        if (ab) return launch_axpby(p, y, nullptr, *ab);
         SPMV_HIP_TRY(hipMemsetAsync(y, 0, sizeof(double) * (size_t)p->m, p->stream));
         return SPMV_SUCCESS;
     }
@@ -215,11 +248,17 @@ int launch_dia(const spmv_plan_s *p, const double *x, double *y) {
     if (const char *e = probe_env("SPMV_LAUNCH_DIA_LDS_KB")) kb = std::atoi(e);
     const int dbg = launch_dbg(d.dbg);
     const bool fits = g.win <= kDiaMaxWin;
-    auto go = [&](auto kernel, bool ldsx) {
+    auto go = [&](auto kernel, bool ldsx, auto... ab_args) {
         const size_t lds = ldsx ? std::max(sizeof(double) * (size_t)g.win, (size_t)kb * 1024) : 0;
         hipLaunchKernelGGL(kernel, g.blocks, dim3(256), lds, p->stream, p->m, d.mp, p->n, d.n_diags, d.off, g.off_min,
-                           ldsx ? (int32_t)g.win : 0, d.val, x, y, d.group);
+                           ldsx ? (int32_t)g.win : 0, d.val, x, y, d.group, ab_args...);
     };
+    if (ab) {  // the product's shape (8 diagonals in flight, nontemporal y) with the axpby epilogue
+        if (fits && !(dbg & 1)) go(dia_axpby_kernel<true>, true, ab->alpha, ab->beta);
+        else go(dia_axpby_kernel<false>, false, ab->alpha, ab->beta);
+        SPMV_HIP_TRY(hipGetLastError());
+        return SPMV_SUCCESS;
+    }
 #ifdef SPMV_PROBES
     if (fits && (dbg & 4)) go(dia_kernel<4, true>, true);  // probe A/B: 4 (dbg 4) / 16 (dbg 8) diagonals in flight per lane
     else if (fits && (dbg & 8)) go(dia_kernel<16, true>, true);

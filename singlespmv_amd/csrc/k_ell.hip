@@ -39,12 +39,17 @@ __device__ __forceinline__ const char *ell_at(const void *base, int64_t byte_off
 }
 
 // UNROLL quads per iteration: 4 UNROLL K doubles of gathers in flight per lane
-template <int K, int UNROLL, bool PERM, bool O32>
+//
+// AB (K = 1, spmv_execute_axpby): the store writes alpha * sum + beta * y0
+// (device.hpp axpby); y0 = Y[row], through perm for JDS, is loaded before the
+// slots like the perm entry itself.
+template <int K, int UNROLL, bool PERM, bool O32, bool AB = false>
 __device__ __forceinline__ void ell_slice_body(int64_t m, int64_t n_slices, const int32_t *__restrict__ perm,
                                                const int64_t *__restrict__ slice_off,
                                                const int32_t *__restrict__ col, const double *__restrict__ val,
                                                const double *__restrict__ X, int64_t ldx, double *__restrict__ Y,
-                                               int64_t ldy) {
+                                               int64_t ldy, double alpha = 0.0, double beta = 0.0) {
+    static_assert(!AB || K == 1, "the axpby epilogue is single-vector");
     const int64_t slice = (int64_t)blockIdx.x * (blockDim.x / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (slice >= n_slices) return;
@@ -52,6 +57,10 @@ __device__ __forceinline__ void ell_slice_body(int64_t m, int64_t n_slices, cons
     // JDS: the matrix row, loaded before the slots so its latency hides
     // behind them instead of trailing the wave
     const int64_t row = PERM ? (srow < m ? (int64_t)perm[srow] : 0) : srow;
+    double y0 = 0.0;
+    if constexpr (AB) {
+        if (srow < m) y0 = ld_stream(Y + row * ldy);
+    }
     const int64_t base = slice_off[slice];
     const int64_t quads = (slice_off[slice + 1] - base) >> 8;  // (width/4)
     const int32_t *cs = col + base;  // wave-uniform slice bases
@@ -112,6 +121,7 @@ __device__ __forceinline__ void ell_slice_body(int64_t m, int64_t n_slices, cons
         add(b.x, g[2]);
         add(b.y, g[3]);
     }
+    if constexpr (AB) acc[0] = axpby(alpha, acc[0], beta, y0);
     if (srow < m) st_row<K>(Y + row * ldy, acc);
 }
 
@@ -125,6 +135,18 @@ __global__ __launch_bounds__(256) void ell_slice_kernel(int64_t m, int64_t n_sli
                                                         const double *__restrict__ x,
                                                         double *__restrict__ y) {
     ell_slice_body<1, UNROLL, PERM, O32>(m, n_slices, perm, slice_off, col, val, x, 1, y, 1);
+}
+
+// y = alpha * A x + beta * y: the single-vector body with the axpby epilogue
+template <int UNROLL, bool PERM, bool O32>
+__global__ __launch_bounds__(256) void ell_slice_axpby_kernel(int64_t m, int64_t n_slices,
+                                                              const int32_t *__restrict__ perm,
+                                                              const int64_t *__restrict__ slice_off,
+                                                              const int32_t *__restrict__ col,
+                                                              const double *__restrict__ val,
+                                                              const double *__restrict__ x, double *__restrict__ y,
+                                                              double alpha, double beta) {
+    ell_slice_body<1, UNROLL, PERM, O32, true>(m, n_slices, perm, slice_off, col, val, x, 1, y, 1, alpha, beta);
 }
 
 template <int K, int UNROLL, bool PERM, bool O32>
@@ -155,18 +177,23 @@ static bool ell_o32(const spmv_plan_s *p, int64_t ldx) {
            (int64_t)p->ell.max_width * 64 * 8 < ((int64_t)1 << 31);
 }
 
-// one launch of K vectors, U quads per iteration (K = 1: ldx = ldy = 1)
+// one launch of K vectors, U quads per iteration (K = 1: ldx = ldy = 1; ab:
+// with the axpby epilogue)
 template <int K, int U>
 static void launch_ell_ku(const spmv_plan_s *p, const double *X, int64_t ldx, double *Y, int64_t ldy, size_t lds,
-                          bool o32) {
+                          bool o32, const Axpby *ab = nullptr) {
     const EllDev &e = p->ell;
     const dim3 blocks((unsigned)((e.n_slices + 3) / 4));
     auto go = [&](auto perm, auto o) {
         constexpr bool P = decltype(perm)::value, O = decltype(o)::value;
-        if constexpr (K == 1)
-            hipLaunchKernelGGL((ell_slice_kernel<U, P, O>), blocks, dim3(256), lds, p->stream, p->m, e.n_slices,
-                               e.perm, e.slice_off, e.col, e.val, X, Y);
-        else
+        if constexpr (K == 1) {
+            if (ab)
+                hipLaunchKernelGGL((ell_slice_axpby_kernel<U, P, O>), blocks, dim3(256), lds, p->stream, p->m,
+                                   e.n_slices, e.perm, e.slice_off, e.col, e.val, X, Y, ab->alpha, ab->beta);
+            else
+                hipLaunchKernelGGL((ell_slice_kernel<U, P, O>), blocks, dim3(256), lds, p->stream, p->m, e.n_slices,
+                                   e.perm, e.slice_off, e.col, e.val, X, Y);
+        } else
             hipLaunchKernelGGL((ell_slice_multi_kernel<K, U, P, O>), blocks, dim3(256), lds, p->stream, p->m,
                                e.n_slices, e.perm, e.slice_off, e.col, e.val, X, ldx, Y, ldy);
     };
@@ -178,7 +205,7 @@ static void launch_ell_ku(const spmv_plan_s *p, const double *X, int64_t ldx, do
     else go_o(std::false_type{});
 }
 
-int launch_ell(const spmv_plan_s *p, const double *x, double *y) {
+int launch_ell(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab) {
     const EllDev &e = p->ell;
     if (e.n_slices == 0) return SPMV_SUCCESS;
     // The product runs 2 quads (4 slots each) per lane per iteration; the
@@ -190,13 +217,13 @@ int launch_ell(const spmv_plan_s *p, const double *x, double *y) {
     int unroll = e.unroll;
     if (const char *v = probe_env("SPMV_LAUNCH_ELL_UNROLL")) unroll = std::atoi(v);
     if (const char *v = probe_env("SPMV_LAUNCH_ELL_LDS_KB")) lds = (size_t)std::atoi(v) * 1024;
-    switch (unroll) {
+    switch (ab ? 2 : unroll) {  // the axpby epilogue: the product's shape only
         case 1: launch_ell_ku<1, 1>(p, x, 1, y, 1, lds, o32); break;
         case 4: launch_ell_ku<1, 4>(p, x, 1, y, 1, lds, o32); break;
-        default: launch_ell_ku<1, 2>(p, x, 1, y, 1, lds, o32);
+        default: launch_ell_ku<1, 2>(p, x, 1, y, 1, lds, o32, ab);
     }
 #else
-    launch_ell_ku<1, 2>(p, x, 1, y, 1, lds, o32);
+    launch_ell_ku<1, 2>(p, x, 1, y, 1, lds, o32, ab);
 #endif
     SPMV_HIP_TRY(hipGetLastError());
     return SPMV_SUCCESS;
