@@ -68,6 +68,25 @@ def expected(s, y0, alpha, beta):
     return np.add(p, q)
 
 
+REFRESH_STRUCTURES = ("staircase", "powerlaw", "uniform16", "banded")
+
+
+@functools.lru_cache(maxsize=None)
+def refresh_cases(name):
+    """(A, B): one structure and one x with two value sets, for a plan built
+    from A and refreshed to B (tests/test_gpu_update_values.py).  B is
+    signed_inputs.case(name, "cancel"); A carries the `spread` family's
+    values on B's x, with its own reference and sequential sums."""
+    import oracle
+    b = si.case(name, "cancel")
+    val = si.case(name, "spread")["val"]
+    ref = si.ref_rows(b["rp"], b["col"], val, b["x"])
+    yo = oracle.csr_spmv(b["rp"], b["col"], np.ascontiguousarray(val), np.ascontiguousarray(b["x"]))
+    for a in (yo,) + ref:
+        a.setflags(write=False)
+    return dict(b, family="spread", val=val, ref=ref, y_oracle=yo), b
+
+
 def bound(rp, ref, y0, alpha, beta):
     """(want, tol) in extended precision: alpha y_hi + beta y0 and
     |alpha| row_tol + 3 * 2^-53 (|alpha| mag + |beta y0|) per row (module

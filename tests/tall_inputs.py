@@ -29,8 +29,14 @@ zeroed in place, after which all of y must be +0.0 bit for bit.  A store at a
 wrapped offset therefore fails twice: a stray non-zero on an empty row, and a
 live row still holding its fill.
 
+y = alpha A x + beta y (check_axpby_y) starts from a y0 that is a formula of
+the row, y0_rows: never zero, another value 2^29, 2^30 and 2^31 rows away, and
+cheap to evaluate on the device a chunk at a time, so every row off the live
+ones is checked bit for bit against beta * y0[r] without an m-sized copy.
+
 Plain helper module (numpy only, besides signed_inputs, special_values,
-wide_inputs and the oracle; torch only inside the device builders and check_y);
+wide_inputs, axpby_inputs and the oracle; torch only inside the device
+builders and the two checks);
 tests/test_tall_inputs.py checks it on the CPU, tests/test_gpu_tall_y.py uses
 it on the GPU.
 """
@@ -38,6 +44,7 @@ import functools
 
 import numpy as np
 
+import axpby_inputs as ai
 import signed_inputs as si
 import special_values as sv
 import wide_inputs as wi
@@ -60,6 +67,11 @@ LONG_ROWS = si.STAIR_LONG  # compact row: entries
 EMPTY_EVERY = 11  # compact row i is empty when i % 11 == 5 (and no row below asks to stay)
 CUMSUM_CHUNK = 1 << 27  # device_csr's cumsum and check_y's count walk the big tensors in pieces of this size
 X_FILL = 1.0  # tall_band: x off the live columns (DIA multiplies its zero slots by it)
+AXPBY = (-2.5, 0.75)  # (alpha, beta) of the one execute_axpby every tall case adds
+# y0[r] = +-((r mod Y0_PERIOD) + 1) / 8192.  The period must not divide 2^29, 2^30 or 2^31 (8191 is prime: they leave
+# 8, 16 and 32), so a y0 loaded that many rows away is another value -- never make it a power of two.  It stays below
+# 8192 so that y0 has at most 13 significant bits and 0.75 * y0 is exact.
+Y0_PERIOD = 8191
 
 
 # ---------------------------------------------------------------- the row map
@@ -315,4 +327,91 @@ def check_y(y_dev, c, what, info=None, col=None, prev=None):
         at = torch.nonzero(y_dev.view(torch.int64))[:5, 0].cpu().tolist() if stray <= 1 << 20 else []
         raise AssertionError(f"{what}: {stray} rows off the live ones are not +0.0, first {at}: "
                              f"{[float(y_dev[r]) for r in at]}")
+    return worst
+
+
+# ---------------------------------------------------------------- y = alpha A x + beta y
+def y0_rows(rows):
+    """y0 on the given rows (numpy): (+1 if r is even else -1) * ((r mod 8191) + 1) / 8192."""
+    r = np.asarray(rows, np.int64)
+    return np.where(r % 2 == 0, 1.0, -1.0) * ((r % Y0_PERIOD + 1).astype(np.float64) / 8192.0)
+
+
+def _y0_chunk(a, b, device, scale=1.0):
+    """scale * y0 on rows [a, b), on `device`.  Evaluated in float64: the rows (< 2^31), fmod and the division by
+    8192 are exact, and so is scale = 0.75 on the 13 bits of y0."""
+    import torch
+    sign = torch.arange(a, b, dtype=torch.float64, device=device).fmod_(2.0).mul_(-2.0).add_(1.0)
+    v = torch.arange(a, b, dtype=torch.float64, device=device).fmod_(float(Y0_PERIOD)).add_(1.0).mul_(1.0 / 8192.0)
+    v.mul_(sign)
+    return v if scale == 1.0 else v.mul_(scale)
+
+
+def fill_y0(y_dev, shift=0):
+    """y_dev[r] = y0[r + shift], CUMSUM_CHUNK rows at a time (`shift`: the CPU tests' planted error)."""
+    for a in range(0, y_dev.numel(), CUMSUM_CHUNK):
+        b = min(a + CUMSUM_CHUNK, y_dev.numel())
+        y_dev[a:b] = _y0_chunk(a + shift, b + shift, y_dev.device)
+
+
+def off_pattern(y_dev, beta):
+    """(how many entries of y_dev are not beta * y0[r] bit for bit, the first five of them), counted
+    CUMSUM_CHUNK rows at a time against the pattern recomputed for the chunk (a chunk with more than 2^20 of
+    them is counted, not listed)."""
+    import torch
+    bits = y_dev.view(torch.int64)
+    count, at = 0, []
+    for a in range(0, bits.numel(), CUMSUM_CHUNK):
+        b = min(a + CUMSUM_CHUNK, bits.numel())
+        diff = bits[a:b] != _y0_chunk(a, b, y_dev.device, beta).view(torch.int64)
+        k = int(torch.count_nonzero(diff))
+        if 0 < k <= 1 << 20 and len(at) < 5:
+            at += (torch.nonzero(diff)[:5 - len(at), 0] + a).cpu().tolist()
+        count += k
+    return count, at
+
+
+def check_axpby_y(y_dev, c, first_live, alpha, beta, what, info):
+    """What every tall test asks of y after execute_axpby(x, y, alpha, beta) on a y that fill_y0 filled (an
+    m-entry tensor, on the device it lives on).  beta * y0 must be exact and non-zero (AXPBY's 0.75 is).
+
+    The live rows, gathered: finite; unless the plan is COO, bit for bit axpby_inputs.expected(first_live, y0,
+    alpha, beta), first_live = the live rows of a plain execute of the same plan -- the header's two rounded
+    multiplies and one rounded add on the plan's own row sums; where signed_inputs.plan_is_sequential, bit for bit
+    expected(y_oracle, ...) too; every plan within axpby_inputs.assert_bound of the extended-precision reference;
+    COO: the rows inside one 128-entry unit bit for bit, as check_y treats them.  Then beta * y0[row] is stored at
+    the live rows, in place, and every entry of y must be bit for bit beta * y0[r], which is what
+    alpha * (+0.0) + beta * y0[r] gives on a row without entries.  Returns the largest err / bound."""
+    import torch
+    rp = c["rp"]
+    lens = np.diff(rp)
+    assert y_dev.dim() == 1 and y_dev.numel() == c["m"] and y_dev.dtype == torch.float64
+    idx = torch.from_numpy(np.array(c["rowmap"])).to(y_dev.device)
+    y = y_dev[idx].cpu().numpy()
+    bad = ~np.isfinite(y)
+    assert not bad.any(), (f"{what}: axpby: {int(bad.sum())} live rows are not finite, first compact rows "
+                           f"{np.flatnonzero(bad)[:5].tolist()} (rows {c['rowmap'][bad][:5].tolist()})")
+    y0 = y0_rows(c["rowmap"])
+    off = np.multiply(np.float64(beta), y0)
+    assert np.array_equal(ai.expected(np.zeros(len(y0)), y0, alpha, beta), off) and (off != 0).all()
+
+    def same(want, rows, why):
+        d = np.flatnonzero((ai.bits(y) != ai.bits(want)) & rows)
+        assert not len(d), (f"{what}: axpby: {len(d)} live rows are not {why}, first compact rows {d[:5].tolist()} "
+                            f"(rows {c['rowmap'][d[:5]].tolist()}): {y[d[:5]].tolist()} vs {want[d[:5]].tolist()}")
+
+    want = ai.expected(first_live, y0, alpha, beta)
+    if info["format"] == "coo":
+        # f64 atomics: only a row inside one 128-entry unit (and a row without entries) gets its sum in one piece
+        same(want, (rp[:-1] // 128 == (rp[1:] - 1) // 128) | (lens == 0), "expected(execute) inside one unit")
+    else:
+        same(want, np.ones(len(y), bool), "expected(execute): alpha * s + beta * y0 on the plan's own row sums")
+    if si.plan_is_sequential(info):
+        same(ai.expected(c["y_oracle"], y0, alpha, beta), np.ones(len(y), bool), "expected(sequential sum)")
+    worst = ai.assert_bound(y, rp, c["ref"], y0, alpha, beta, what + ": axpby")
+    y_dev[idx] = torch.from_numpy(off).to(y_dev.device)
+    stray, at = off_pattern(y_dev, beta)
+    if stray:
+        raise AssertionError(f"{what}: axpby: {stray} rows off the live ones are not beta * y0, first {at}: "
+                             f"{[float(y_dev[r]) for r in at]} vs {(beta * y0_rows(at)).tolist()}")
     return worst

@@ -96,3 +96,22 @@ def test_bound_formula():
     # beta = 0: y0 is not looked at
     want0, tol0 = ai.bound(rp, (y_hi, mag), np.full(3, np.nan), -2.0, -0.0)
     assert np.array_equal(want0, -2 * y_hi) and np.array_equal(tol0, 2 * rt + 3 * np.longdouble(U) * 2 * mag)
+
+
+@pytest.mark.parametrize("name", ai.REFRESH_STRUCTURES)
+def test_refresh_cases_differ_on_most_rows(name):
+    """The two value sets of refresh_cases share the pattern and x, each
+    passes its own bound, and with the reference alone y = -2.5 A x + 0.75 y0
+    differs between them on at least half of the non-empty rows (here: on all
+    of them) -- a refreshed plan that still computed with A cannot pass as B."""
+    a, b = ai.refresh_cases(name)
+    assert a["rp"] is b["rp"] and a["col"] is b["col"] and a["x"] is b["x"] and a["val"].shape == b["val"].shape
+    assert not np.array_equal(a["val"], b["val"])
+    y0 = ai.y0(b["m"])
+    ya, yb = (ai.expected(c["y_oracle"], y0, -2.5, 0.75) for c in (a, b))
+    for c, y in ((a, ya), (b, yb)):
+        assert ai.assert_bound(y, c["rp"], c["ref"], y0, -2.5, 0.75, f"{name} {c['family']}") <= 1.0
+    live = np.diff(b["rp"]) > 0
+    assert np.array_equal(ai.bits(ya[~live]), ai.bits(yb[~live]))
+    assert (ai.bits(ya) != ai.bits(yb))[live].all()
+    assert len(ai.failing_rows(ya, b["rp"], b["ref"], y0, -2.5, 0.75)[0]) >= live.sum() // 2  # and far beyond B's bound

@@ -10,8 +10,13 @@ per-row arrays are big.  Nothing of size m lives on the host: the row pointers
 are a cumsum on the device, the plans are built there (Plan.from_device_csr),
 and y is judged there -- the live rows within signed_inputs.row_tol of the
 extended-precision reference, bit for bit the oracle's sequential sum where
-the plan is sequential, every other row +0.0 exactly.  One row_ptr and one y
-are alive per size (peak about 35 GiB in the default selection; m = 2^31 - 2
+the plan is sequential, every other row +0.0 exactly.  Every execute case then
+runs y = -2.5 A x + 0.75 y once on the same plan and y (tall_inputs.y0_rows,
+check_axpby_y): the fused CSR / ELL / JDS / DIA kernels' load of y[row], and
+the generic path's scratch of m + 2 doubles with axpby_kernel over all m rows;
+test_tall_axpby_zero runs that kernel on plans with nothing stored.  One
+row_ptr and one y are alive per size (peak about 38 GiB in the default
+selection; m = 2^31 - 2
 for every format, and ELL, BIN, AUTO and DIA at 2^30 rows, are opt-in,
 SPMV_HUGE_TESTS=1, about 100 GiB; profiles/tall_y/README.md has the measured
 lines and why the default selection is cut as it is).  Needs an MI355X:
@@ -73,7 +78,9 @@ def tall_buf(request):
     """The device buffers of one (m, ld, rp?, extra), module-scoped and
     parametrised as test_gpu_wide_x.wide_buf: each parameter is torn down (its
     memory returned to the device) before the next is set up.  `extra`: what
-    the largest plan of the size adds (DIA: x and three diagonals of m)."""
+    the largest plan of the size adds (DIA: x and three diagonals of m; the
+    execute cases: the m + 2 doubles a generic plan's execute_axpby
+    allocates), so that a device too small for a case skips it at set-up."""
     import torch
     m, ld, with_rp, extra = request.param
     need = 8 * m * ld + (8 * (m + 1) if with_rp else 0) + extra
@@ -119,6 +126,27 @@ def _execute_twice(plan, x, y, c, what):
     return worst, first
 
 
+def _axpby_path(info):
+    """The path spmv_execute_axpby takes on a plan of this format: CSR, ELL, DIA and JDS without overflow rows
+    have one writer per row and take alpha and beta in their store."""
+    fused = info["format"] in ("csr", "ell", "dia") or (info["format"] == "jds" and info["overflow_nnz"] == 0)
+    return "fused" if fused else "generic"
+
+
+def _axpby(plan, x, y, c, first, what):
+    """One execute_axpby(x, y, -2.5, 0.75) on the m-entry y filled with tall_inputs' y0, `first` the live rows of
+    the plain execute: the path the plan must take, the scratch of m + 2 doubles a generic plan allocates for it,
+    and tall_inputs.check_axpby_y.  Returns (the path, the largest err / bound)."""
+    info = plan.info()
+    path = plan.axpby_path()
+    assert path == _axpby_path(info), (what, info["format"], path)
+    ti.fill_y0(y)
+    plan.execute_axpby(x, y, *ti.AXPBY)
+    grown = plan.info()["device_bytes"] - info["device_bytes"]
+    assert grown >= 8 * c["m"] if path == "generic" else grown == 0, (what, path, grown)
+    return path, ti.check_axpby_y(y, c, first, *ti.AXPBY, what, info)
+
+
 def _only_live(y, c, what):
     """The live rows of y; every other row must be +0.0 (y's live rows are
     zeroed in place on the way)."""
@@ -151,8 +179,14 @@ def _cases(keep):
             for name in ti.STRUCTURES for cid, fmt, kw in TALL_CONFIGS if keep(fmt)]
 
 
-SIZES = [_buf(T - 1), _buf(T + 4099), _buf(4 * T - 2, marks=HUGE)]
-# DIA: x (8 m) and three diagonals of m rows rounded up to 512 (24 m) on top
+def _scratch(m):
+    """What the first execute_axpby adds to a generic plan: its scratch of m + 2 doubles."""
+    return 8 * (m + 2)
+
+
+SIZES = [_buf(T - 1, extra=_scratch(T - 1)), _buf(T + 4099, extra=_scratch(T + 4099)),
+         _buf(4 * T - 2, extra=_scratch(4 * T - 2), marks=HUGE)]
+# DIA: x (8 m) and three diagonals of m rows rounded up to 512 (24 m) on top; its axpby is fused, no scratch
 DIA_SIZES = [_buf(T - 1, extra=32 * T), _buf(T + 4099, extra=32 * T), _buf(2 * T + 4099, extra=64 * T, marks=HUGE),
              _buf(4 * T - 2, extra=128 * T, marks=HUGE)]
 
@@ -192,8 +226,9 @@ def _assert_path(name, fmt, kw, info, c):
         assert info["ell_width"] == -(-int(lens.max()) // 4) * 4  # whole 4-entry chunks
 
 
-def _line(what, info, worst, t0):
-    print(f"tall-y {what} format={info['format']} kernel={info['kernel']} err/row_tol={worst:.3f} "
+def _line(what, info, worst, t0, axpby=None):
+    ab = "" if axpby is None else f"axpby={axpby[0]} err/bound={axpby[1]:.3f} "
+    print(f"tall-y {what} format={info['format']} kernel={info['kernel']} err/row_tol={worst:.3f} {ab}"
           f"device-used={_used_gib():.1f}GiB wall={time.perf_counter() - t0:.1f}s")
 
 
@@ -217,8 +252,10 @@ def _execute_case(buf, name, fmt, kw, what):
     info = plan.info()
     assert plan.built_on_device()
     _assert_path(name, fmt, kw, info, c)
-    worst, _ = _execute_twice(plan, ti.device_x(c, "cuda"), buf.y, c, what)
-    _line(what, info, worst, t0)
+    x = ti.device_x(c, "cuda")
+    worst, first = _execute_twice(plan, x, buf.y, c, what)
+    ab = _axpby(plan, x, buf.y, c, first, what)
+    _line(what, info, worst, t0, ab)
     plan.destroy()
 
 
@@ -231,7 +268,7 @@ def test_tall_execute(tall_buf, name, fmt, kw, request):
 
 
 @pytest.mark.parametrize("name,fmt,kw", _cases(lambda fmt: fmt in ROWS4))
-@pytest.mark.parametrize("tall_buf", [_buf(2 * T + 4099)], indirect=True)
+@pytest.mark.parametrize("tall_buf", [_buf(2 * T + 4099, extra=_scratch(2 * T + 4099))], indirect=True)
 def test_tall_execute_rows4(tall_buf, name, fmt, kw, request):
     """Rows beyond 2^30 on the formats whose per-row arrays hold 4-byte
     entries (the others at this size: opt-in, below)."""
@@ -239,7 +276,7 @@ def test_tall_execute_rows4(tall_buf, name, fmt, kw, request):
 
 
 @pytest.mark.parametrize("name,fmt,kw", _cases(lambda fmt: fmt not in ROWS4))
-@pytest.mark.parametrize("tall_buf", [_buf(2 * T + 4099, marks=HUGE)], indirect=True)
+@pytest.mark.parametrize("tall_buf", [_buf(2 * T + 4099, extra=_scratch(2 * T + 4099), marks=HUGE)], indirect=True)
 def test_tall_execute_rows8(tall_buf, name, fmt, kw, request):
     """Rows beyond 2^30 on ELL, BIN and AUTO."""
     _execute_case(tall_buf, name, fmt, kw, request.node.callspec.id)
@@ -435,4 +472,38 @@ def test_tall_multi_zero(tall_buf, request):
         plan.execute_multi(X, Y)  # raises unless the call returns success
         assert ti.nonzero_bits(tall_buf.y) == 0, "Y is not +0.0 everywhere"
     _line(request.node.callspec.id + " multi-zero", info, 0.0, t0)
+    plan.destroy()
+
+
+@pytest.mark.parametrize("fmt", ["csr", "dia"])
+@pytest.mark.parametrize("tall_buf", [_buf(T + 4099, LDY, with_rp=False)], indirect=True)
+def test_tall_axpby_zero(tall_buf, fmt, request):
+    """execute_axpby on a plan with nothing stored (CSR with nnz = 0, DIA
+    without a diagonal), m = 2^29 + 4099: axpby_kernel without row sums over
+    all m rows, on the first m entries of multi-zero's buffer.  Every row is
+    bit for bit 0.75 * y0[r] = alpha * (+0.0) + beta * y0[r]; the entry after
+    the last row keeps its fill."""
+    import torch
+    t0 = time.perf_counter()
+    what = request.node.callspec.id
+    m, n = tall_buf.m, 8
+    rp = torch.zeros(m + 1, dtype=torch.int64, device="cuda")
+    plan = sp.Plan.from_device_csr(m, n, rp, torch.zeros(0, dtype=torch.int32, device="cuda"),
+                                   torch.zeros(0, dtype=torch.float64, device="cuda"), fmt=fmt)
+    rp.untyped_storage().resize_(0)
+    del rp
+    torch.cuda.empty_cache()
+    info = plan.info()
+    assert info["format"] == fmt and info["nnz"] == 0 and plan.axpby_path() == "fused"
+    x = torch.full((n,), float("nan"), dtype=torch.float64, device="cuda")  # never read
+    y = tall_buf.y[:m]
+    ti.fill_y0(y)
+    tall_buf.y[m] = SENTINEL
+    plan.execute_axpby(x, y, *ti.AXPBY)
+    assert plan.info()["device_bytes"] == info["device_bytes"]  # no scratch
+    stray, at = ti.off_pattern(y, ti.AXPBY[1])
+    assert stray == 0, (f"{what}: {stray} rows are not 0.75 * y0, first {at}: {[float(y[r]) for r in at]} vs "
+                        f"{(ti.AXPBY[1] * ti.y0_rows(at)).tolist()}")
+    assert float(tall_buf.y[m]) == SENTINEL, f"{what}: the entry after the last row was written"
+    _line(what + " axpby-zero", info, 0.0, t0, ("fused", 0.0))
     plan.destroy()

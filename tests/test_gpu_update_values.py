@@ -3,11 +3,14 @@ spmv_plan_update_prepare / spmv_plan_update_values): an updated plan is, array
 by array (spmv_plan_digest), the plan a fresh build from the new values gives,
 for every format and option set below, on the suite's seven structures; the
 padding and sign rules, the refusals (wrong pattern, merged entries, not
-prepared), alignment and tail cases, streams, graphs, multi executes and the
-memory accounting of include/spmv_hip.h "value refresh"."""
+prepared), alignment and tail cases, streams, graphs, multi executes (fused
+and column by column), execute_axpby on a refreshed plan that already holds
+its scratch, and the memory accounting of include/spmv_hip.h "value
+refresh"."""
 import numpy as np
 import pytest
 
+import axpby_inputs as ai
 import signed_inputs as si
 import singlespmv_amd as sp
 
@@ -396,7 +399,111 @@ def test_fused_multi_sees_the_new_values(fmt):
         assert np.array_equal(Y[:, j], _run(F1, X[:, j])), (fmt, j)
 
 
-# ---- 8. memory accounting -----------------------------------------------------------
+@pytest.mark.parametrize("fmt", ["csr", "bin"])
+def test_columnwise_multi_sees_the_new_values(fmt):
+    """The column-by-column execute_multi (one generic execute per column
+    through the plan's pack and unpack buffers) on a refreshed plan."""
+    torch = _torch()
+    c0, c1 = si.case("banded", "spread"), si.case("banded", "cancel")
+    m, n, rp, col = c1["m"], c1["n"], c1["rp"], c1["col"]
+    P, F1 = _build(m, n, rp, col, c0["val"], fmt, {}, True), _build(m, n, rp, col, c1["val"], fmt, {}, True)
+    rng = np.random.default_rng(8)
+    X = rng.choice([-1.0, 1.0], (n, 3)) * rng.uniform(0.5, 2.0, (n, 3))
+    dX = _dev(X)
+
+    def multi(plan):
+        dY = torch.full((m, 3), float("nan"), dtype=torch.float64, device="cuda")
+        assert plan.multi_path(dX, dY) == [1, 1, 1]
+        plan.execute_multi(dX, dY)
+        return dY.cpu().numpy()
+
+    Y_old = multi(P)  # the pack and unpack buffers exist before the refresh
+    P.prepare_update(_dev(rp), _dev(col))
+    P.update_values(_dev(c1["val"]))
+    Y, Y_fresh = multi(P), multi(F1)
+    assert np.array_equal(Y, Y_fresh) and not np.array_equal(Y, Y_old), fmt
+    for j in range(3):
+        assert np.array_equal(Y[:, j], _run(F1, X[:, j])), (fmt, j)
+    for q in (P, F1):
+        q.destroy()
+
+
+# ---- 8. axpby after update ----------------------------------------------------------
+# the three CSR kernels (uniform16: slab2, banded: slabx, powerlaw: adaptive), sliced ELL with and without perm and
+# DIA take alpha and beta in their store; the others run into the plan's scratch, which the first call allocates
+AXPBY_AFTER_UPDATE = [("uniform16", "csr", {"csr_lanes": 0}, "csr_slab2_kernel"),
+                      ("banded", "csr", {"csr_lanes": 0}, "csr_slabx_kernel"),
+                      ("powerlaw", "csr", {"csr_lanes": 0}, "csr_adaptive_kernel"),
+                      ("uniform16", "ell", {}, "ell_slice_kernel"),
+                      ("staircase", "jds", {"ell_width": 9000}, "ell_slice_kernel<perm>"),  # no overflow rows
+                      ("banded", "dia", {}, None), ("powerlaw", "ss", {}, None), ("powerlaw", "hyb", {}, None),
+                      ("powerlaw", "css", {}, None), ("powerlaw", "bin", {}, None), ("powerlaw", "coo", {}, None)]
+AB = (-2.5, 0.75)
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+@pytest.mark.parametrize("name,fmt,kw,kernel", AXPBY_AFTER_UPDATE, ids=[f"{a[0]}-{a[1]}" for a in AXPBY_AFTER_UPDATE])
+def test_axpby_sees_the_new_values(name, fmt, kw, kernel, device):
+    """execute_axpby on a plan refreshed from values A to values B is, bit for
+    bit, execute_axpby on a plan built from B (COO: within
+    axpby_inputs.assert_bound, and bit for bit on the rows inside one
+    128-entry unit), and back again.  The plan has run execute_axpby before
+    the refresh, so a generic plan already owns its scratch: the refreshed
+    layout still digests as the fresh one's, and device_bytes does not move
+    across update_values (host values: by the staging buffer of 8 nnz, once)
+    nor across the next execute_axpby -- nothing was allocated anew."""
+    torch = _torch()
+    cA, cB = ai.refresh_cases(name)
+    m, n, rp, col, nnz = cB["m"], cB["n"], cB["rp"], cB["col"], len(cB["col"])
+    what = f"{name} {fmt} {'device' if device else 'host'}"
+    P, FA, FB = (_build(m, n, rp, col, v, fmt, kw, device) for v in (cA["val"], cA["val"], cB["val"]))
+    info = P.info()
+    fused = fmt in ("csr", "ell", "dia", "jds")
+    assert info["format"] == fmt and (kernel is None or info["kernel"].startswith(kernel)), info["kernel"]
+    assert P.axpby_path() == ("fused" if fused else "generic") and (fmt != "jds" or info["overflow_nnz"] == 0)
+    digest_B = FB.digest()  # before FB's own execute_axpby: without a scratch
+    dx, y0 = _dev(cB["x"]), ai.y0(m)
+
+    def axpby(plan):
+        dy = _dev(y0)
+        plan.execute_axpby(dx, dy, *AB)
+        return dy.cpu().numpy()
+
+    def same(y, fresh, c, tag):
+        rows = np.ones(m, bool)
+        if fmt == "coo":  # unordered f64 atomics: only a row inside one unit gets its sum in one piece
+            rows = (rp[:-1] // 128 == (rp[1:] - 1) // 128) | (np.diff(rp) == 0)
+            ai.assert_bound(fresh, rp, c["ref"], y0, *AB, f"{what} {tag} fresh")
+        bad = np.flatnonzero((ai.bits(y) != ai.bits(fresh)) & rows)
+        assert not len(bad), (f"{what} {tag}: {len(bad)} rows differ from the fresh plan's, first {bad[:5].tolist()}: "
+                              f"{y[bad[:3]].tolist()} vs {fresh[bad[:3]].tolist()}")
+        ai.assert_bound(y, rp, c["ref"], y0, *AB, f"{what} {tag}")
+
+    b_built = info["device_bytes"]
+    y_A = axpby(P)
+    b0 = P.info()["device_bytes"]
+    assert b0 - b_built == 0 if fused else b0 - b_built >= 8 * m, (what, b0 - b_built)
+    same(y_A, axpby(FA), cA, "before the refresh")
+    P.prepare_update(*((_dev(rp), _dev(col)) if device else (rp, col)))
+    b1 = P.info()["device_bytes"]
+    P.update_values(_dev(cB["val"]) if device else np.ascontiguousarray(cB["val"]))
+    b2 = P.info()["device_bytes"]
+    assert b2 - b1 == (0 if device else 8 * nnz), (what, b2 - b1)
+    _same_layout(P.digest(), digest_B, what + " after update_values(B), holding the scratch")
+    y_B = axpby(P)
+    assert P.info()["device_bytes"] == b2, f"{what}: execute_axpby allocated again after the refresh"
+    same(y_B, axpby(FB), cB, "after update_values(B)")
+    stale = ai.bits(y_B) == ai.bits(y_A)
+    live = np.diff(rp) > 0
+    assert 2 * int((~stale & live).sum()) >= int(live.sum()), f"{what}: {int(stale[live].sum())} rows kept A's result"
+    P.update_values(_dev(cA["val"]) if device else np.ascontiguousarray(cA["val"]))
+    assert P.info()["device_bytes"] == b2
+    same(axpby(P), y_A, cA, "after update_values(A)")
+    for q in (P, FA, FB):
+        q.destroy()
+
+
+# ---- 9. memory accounting -----------------------------------------------------------
 def _value_slots(info, nnz):
     """(value slots, value arrays) of a plan, from the layouts of
     include/spmv_hip.h: CSR nnz (rounded up to 256 in the row-group order)

@@ -7,12 +7,15 @@ entries except on the columns a layout may multiply, so a read at a wrapped or
 sign-extended offset poisons its row wherever it lands: y must be finite on
 every row, within signed_inputs.row_tol of the extended-precision reference on
 the compact columns, and bit for bit the oracle's sequential sum where the
-plan is sequential.  One device x is alive at a time (peak about 20 GiB in the
+plan is sequential.  Every test_wide_execute case then runs
+y = -2.5 A x + 0.75 y once on the same plan and x: the fused kernels choose
+their x addressing on their own.  One device x is alive at a time (peak about 20 GiB in the
 multi-vector case of 16 GiB).  Needs an MI355X: `pytest -m gpu`.
 """
 import numpy as np
 import pytest
 
+import axpby_inputs as ai
 import signed_inputs as si
 import singlespmv_amd as sp
 import special_values as sv
@@ -24,6 +27,7 @@ pytestmark = pytest.mark.gpu
 
 W = wi.WIDE
 GIB = 1 << 30
+AXPBY = (-2.5, 0.75)  # (alpha, beta) of the one execute_axpby of every test_wide_execute case
 
 
 def _nid(n):
@@ -119,6 +123,35 @@ def _check_y(plan, c, ya, yb, what, col=None):
     return worst
 
 
+def _check_axpby(plan, c, x, ya, what):
+    """One execute_axpby(x, y, -2.5, 0.75) on a device copy of
+    axpby_inputs.y0(m), ya = the plan's plain execute: the fused twins choose
+    their x addressing again (CSR, ELL, DIA; JDS without overflow rows), every
+    other plan runs its own kernels into its scratch.  Bit for bit
+    expected(ya, y0, ...) (COO: on the rows inside one 128-entry unit), and
+    every plan within axpby_inputs.assert_bound on the compact arrays.
+    Returns (the path, the largest err / bound)."""
+    import torch
+    info, m, rp = plan.info(), c["m"], c["rp"]
+    fused = info["format"] in ("csr", "ell", "dia") or (info["format"] == "jds" and info["overflow_nnz"] == 0)
+    path = plan.axpby_path()
+    assert path == ("fused" if fused else "generic"), (what, info["format"], path)
+    y0 = ai.y0(m)
+    yd = torch.from_numpy(np.array(y0)).cuda()
+    plan.execute_axpby(x, yd, *AXPBY)
+    y = yd.cpu().numpy()
+    assert np.isfinite(y).all(), (f"{what}: axpby: {int((~np.isfinite(y)).sum())} rows read x outside the reach, "
+                                  f"first {np.flatnonzero(~np.isfinite(y))[:5].tolist()}")
+    rows = np.ones(m, bool)
+    if info["format"] == "coo":  # f64 atomics: only a row inside one unit gets its sum in one piece
+        rows = (rp[:-1] // 128 == (rp[1:] - 1) // 128) | (np.diff(rp) == 0)
+    want = ai.expected(ya, y0, *AXPBY)
+    bad = np.flatnonzero((ai.bits(y) != ai.bits(want)) & rows)
+    assert not len(bad), (f"{what}: axpby: {len(bad)} rows are not expected(execute), first {bad[:5].tolist()}: "
+                          f"{y[bad[:3]].tolist()} vs {want[bad[:3]].tolist()}")
+    return path, ai.assert_bound(y, rp, c["ref"], y0, *AXPBY, what + ": axpby")
+
+
 def _host_plan(c, fmt, kw):
     return sp.Plan.from_csr(c["m"], c["n"], c["rp"], c["col"], c["val"], fmt, build="host", **kw)
 
@@ -188,11 +221,13 @@ def test_wide_execute(wide_buf, name, fmt, kw, request):
     plan = _host_plan(c, fmt, kw)
     info = plan.info()
     _assert_path(name, fmt, kw, info, c)
-    ya, yb = _execute_twice(plan, wide_buf.x(c), c["m"])
+    x = wide_buf.x(c)
+    ya, yb = _execute_twice(plan, x, c["m"])
     worst = _check_y(plan, c, ya, yb, what)
     assert (sv.bits(ya[np.diff(c["rp"]) == 0]) == 0).all(), f"{what}: an empty row is not +0.0"
+    path, worst_ab = _check_axpby(plan, c, x, ya, what)
     print(f"wide-x {what} format={info['format']} kernel={info['kernel']} err/row_tol={worst:.3f} "
-          f"device-used={_used_gib():.1f}GiB")
+          f"axpby={path} err/bound={worst_ab:.3f} device-used={_used_gib():.1f}GiB")
     plan.destroy()
 
 

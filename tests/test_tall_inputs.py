@@ -1,7 +1,9 @@
 """CPU checks of tests/tall_inputs.py: the row map holds the rows it promises
 at every size, the spread CSR is the compact one scattered through it, the
 reference alone passes check_y on every structure, and check_y rejects a y
-whose stores wrapped -- what keeps tests/test_gpu_tall_y.py honest.
+whose stores wrapped; the y0 formula of the axpby step is what its comment
+says, the reference alone passes check_axpby_y and a y0 loaded or a y stored
+rows away does not -- what keeps tests/test_gpu_tall_y.py honest.
 """
 import numpy as np
 import pytest
@@ -203,3 +205,145 @@ def test_check_y_rejects_planted_errors(name, fill):
     with pytest.raises(AssertionError, match="held before"):
         ti.check_y(y.clone(), c, name, prev=prev)
     ti.check_y(y, c, name)  # within row_tol all the same
+
+
+# ---------------------------------------------------------------- y = alpha A x + beta y
+def test_y0_formula():
+    """Never zero, at most 13 significant bits (beta * y0 exact), another value 2^29, 2^30 and 2^31 rows away,
+    and the device evaluation chunk by chunk is the numpy one bit for bit."""
+    import torch
+    T = ti.TALL
+    assert [(1 << p) % ti.Y0_PERIOD for p in (29, 30, 31)] == [8, 16, 32]
+    rows = np.concatenate([np.arange(0, 3 * ti.Y0_PERIOD), ti.rowmap(4 * T - 2), [4 * T - 3]])
+    y0 = ti.y0_rows(rows)
+    P = ti.Y0_PERIOD
+    assert y0[0] == 1 / 8192 and y0[1] == -2 / 8192 and y0[P - 1] == 8191 / 8192 and y0[P] == -1 / 8192
+    assert (y0 != 0).all() and (np.abs(y0) < 1).all() and (np.sign(y0) == np.where(rows % 2 == 0, 1, -1)).all()
+    assert np.array_equal(y0 * 8192, np.rint(y0 * 8192))  # k / 8192 with k <= 8191: 13 bits
+    beta = ti.AXPBY[1]
+    exact = (beta * y0).astype(np.longdouble) == np.longdouble(beta) * y0.astype(np.longdouble)
+    assert exact.all()
+    for p in (29, 30, 31):
+        far = rows[rows + (1 << p) < 1 << 32]
+        assert (ti.y0_rows(far + (1 << p)) != ti.y0_rows(far)).all(), p
+    for a, b in ((0, 20000), (T - 5, T + 9000), (4 * T - 9000, 4 * T - 2)):
+        r = np.arange(a, b)
+        assert np.array_equal(sv.bits(ti._y0_chunk(a, b, "cpu").numpy()), sv.bits(ti.y0_rows(r)))
+        assert np.array_equal(sv.bits(ti._y0_chunk(a, b, "cpu", beta).numpy()), sv.bits(beta * ti.y0_rows(r)))
+    y = torch.empty(ti.CPU_M, dtype=torch.float64)
+    ti.fill_y0(y)
+    assert np.array_equal(sv.bits(y.numpy()), sv.bits(ti.y0_rows(np.arange(ti.CPU_M))))
+
+
+def _axpby_y(c, s=None, shift=0):
+    """The reference's own y after y = alpha A x + beta y0 on all m rows: expected(s, y0, ...) on the live rows
+    (s: the oracle's sums), beta * y0 elsewhere."""
+    import torch
+    import axpby_inputs as ai
+    s = c["y_oracle"] if s is None else s
+    y = torch.empty(c["m"], dtype=torch.float64)
+    ti.fill_y0(y, shift)
+    y.mul_(ti.AXPBY[1])
+    live = ai.expected(s, ti.y0_rows(c["rowmap"] + shift), *ti.AXPBY)
+    y[torch.from_numpy(np.array(c["rowmap"]))] = torch.from_numpy(live)
+    return y
+
+
+def _nudged(c, s, rows):
+    """s with a quarter of row_tol added on `rows`: inside the axpby bound, and far above the last bit of
+    alpha * s + beta * y0 (the cancel family's sums are rounding noise, one ulp of s would vanish in the add)."""
+    s2 = np.array(s)
+    s2[rows] += 0.25 * np.asarray(si.row_tol(c["rp"], c["ref"][1]), np.float64)[rows]
+    return s2
+
+
+class _Coo(_Info):
+    def __init__(self):
+        super().__init__()
+        self["format"] = "coo"
+
+
+@pytest.mark.parametrize("name", ALL)
+def test_reference_passes_check_axpby_y(name, monkeypatch):
+    c = ti.case(name, ti.CPU_M)
+    s = c["y_oracle"]
+    assert ti.check_axpby_y(_axpby_y(c), c, s, *ti.AXPBY, name, _Info()) <= 1.0
+    monkeypatch.setattr(ti, "CUMSUM_CHUNK", 4099)  # chunks far smaller than m
+    y = _axpby_y(c)
+    assert ti.check_axpby_y(y, c, s, *ti.AXPBY, name, _Info()) <= 1.0
+    want = ti.AXPBY[1] * ti.y0_rows(np.arange(c["m"]))
+    assert np.array_equal(sv.bits(y.numpy()), sv.bits(want))  # the live rows were overwritten in place
+    # COO: a row split across units may differ from expected(execute) inside the bound; a row of one unit may not
+    rp = c["rp"]
+    split = np.flatnonzero(rp[:-1] // 128 != (rp[1:] - 1) // 128)
+    inside = np.flatnonzero((rp[:-1] // 128 == (rp[1:] - 1) // 128) & (np.diff(rp) > 0) & (s != 0))
+    for rows, info, ok in ((split[:1], _Coo(), True), (split[:1], _Info(), False), (inside[:1], _Coo(), False)):
+        if not len(rows):
+            assert name == "tall_uniform"  # rows of 16 entries never straddle a unit
+            continue
+        s2 = _nudged(c, s, rows)
+        if ok:
+            ti.check_axpby_y(_axpby_y(c), c, s2, *ti.AXPBY, name, info)
+        else:
+            with pytest.raises(AssertionError, match=r"expected\(execute\)"):
+                ti.check_axpby_y(_axpby_y(c), c, s2, *ti.AXPBY, name, info)
+
+
+@pytest.mark.parametrize("name", ALL)
+def test_check_axpby_y_rejects_planted_errors(name):
+    """One off-live row keeps y0, one live row takes the value of the row 8 below it (a y0 load or a store 2^29
+    rows away at the period's remainder), one off-live row is +0.0 (execute's store, not axpby's), y0 shifted by
+    one row; and a sequential plan off the oracle's sum, a live row not finite."""
+    c = ti.case(name, ti.CPU_M)
+    s = c["y_oracle"]
+    lens = np.diff(c["rp"])
+    rowmap = c["rowmap"]
+
+    def check(y, info=None, first=s):
+        return ti.check_axpby_y(y, c, first, *ti.AXPBY, name, info or _Info())
+
+    for row in (1 if 1 not in rowmap else 3000, c["m"] // 2, c["m"] - 5000):
+        assert row not in rowmap
+        y = _axpby_y(c)
+        y[row] = float(ti.y0_rows([row])[0])
+        with pytest.raises(AssertionError, match=rf"1 rows off the live ones are not beta \* y0, first \[{row}\]"):
+            check(y)
+        y = _axpby_y(c)
+        y[row] = 0.0
+        with pytest.raises(AssertionError, match=r"off the live ones are not beta \* y0"):
+            check(y)
+    live = np.flatnonzero((lens > 0) & (rowmap >= 8))
+    cut = live[c["rp"][live] // 128 != (c["rp"][live + 1] - 1) // 128]
+    assert len(cut) or name == "tall_uniform"  # tall_uniform's rows of 16 entries never straddle a unit
+    for i in [int(live[0]), int(live[-1])] + cut[:1].tolist():
+        r = int(rowmap[i])
+        y = _axpby_y(c)
+        y[r] = y[r - 8].clone()
+        with pytest.raises(AssertionError, match=r"expected\(execute\)"):
+            check(y)
+        split = c["rp"][i] // 128 != (c["rp"][i + 1] - 1) // 128  # COO: the bound alone judges a row split across units
+        with pytest.raises(AssertionError, match="beyond the axpby bound" if split else r"expected\(execute\)"):
+            check(y, _Coo())
+        y = _axpby_y(c)  # the right sum on the y0 of the row 8 below
+        y[r] = float(ti.AXPBY[0] * s[i] + ti.AXPBY[1] * ti.y0_rows([r - 8])[0])
+        with pytest.raises(AssertionError, match=r"expected\(execute\)"):
+            check(y)
+    with pytest.raises(AssertionError, match=r"expected\(execute\)|off the live ones"):
+        check(_axpby_y(c, shift=1))
+    y = _axpby_y(c, shift=1)  # the live rows right, y0 shifted everywhere else
+    import torch
+    idx = torch.from_numpy(np.array(rowmap))
+    y[idx] = _axpby_y(c)[idx]
+    with pytest.raises(AssertionError, match=r"off the live ones are not beta \* y0"):
+        check(y)
+    i = int(live[-1])
+    s2 = _nudged(c, s, [i])
+    with pytest.raises(AssertionError, match=r"expected\(sequential sum\)"):
+        check(_axpby_y(c, s2), first=s2)
+    info = _Info()
+    info["format"], info["css_split_rows"] = "css", 1  # not sequential: the plan's own sums are the reference
+    check(_axpby_y(c, s2), info, first=s2)
+    y = _axpby_y(c)
+    y[int(rowmap[i])] = float("nan")
+    with pytest.raises(AssertionError, match="not finite"):
+        check(y)
