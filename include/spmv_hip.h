@@ -267,6 +267,87 @@ int spmv_plan_create_csr32_device(int32_t m, int32_t n, int32_t nnz, const int32
                                   const int32_t *d_col_idx, const double *d_val,
                                   const spmv_options_t *opt, spmv_plan_t *plan);
 
+/* ---- the transpose: y = A^T x ----------------------------------------------
+ * Every format here is a row layout with one writer per row, so A^T is not
+ * scattered out of a plan of A (f64 atomics, COO speed, no sequential sums):
+ * it gets a plan of its own, built from a CSR of A^T.  The two functions
+ * below make that CSR; the three after them build the plan from A directly.
+ *
+ * The transposition.  Input: a CSR of A, (m, n, nnz, row_ptr int64 [m + 1],
+ * col_idx int32 [nnz], val f64 [nnz]); columns inside a row may be unsorted
+ * and may repeat (whatever spmv_plan_create_csr accepts).  Output: the CSR of
+ * A^T -- t_row_ptr int64 [n + 1], t_col_idx int32 [nnz] (the source row of
+ * each entry), t_val f64 [nnz] -- and perm int64 [nnz], the source entry
+ * index of each output entry.  Output row c holds A's entries of column c in
+ * ascending source entry index (a stable sort of the entries by column), so
+ * every output row is in ascending column order whatever order A's rows were
+ * in, duplicates stay adjacent in source order, and transposing twice returns
+ * a column-sorted CSR unchanged.  Values move as bits (NaN payloads, -0.0,
+ * subnormals, Inf); nothing is added or merged.  val and t_val may both be
+ * NULL (the pattern alone); perm may be NULL.  Outputs must not overlap the
+ * inputs.  The host and the device function give the same bytes.
+ *
+ * Refusals, in this order, all SPMV_ERROR_INVALID_VALUE with the outputs
+ * untouched: val without t_val or the reverse; a NULL t_row_ptr, or a NULL
+ * t_col_idx with nnz > 0; then spmv_plan_create_csr's input check (negative
+ * or >= 2^31 - 1 dimensions, NULL row_ptr / col_idx, row_ptr[0] != 0,
+ * row_ptr[m] != nnz, decreasing row_ptr, a column outside [0, n)); the device
+ * function checks that every array is device memory on `device`, then runs
+ * the same input check there -- before any kernel indexes by a column.
+ *
+ * The device function serves nnz < 2^31 - 1 (32-bit entry ids) and returns
+ * SPMV_ERROR_NOT_SUPPORTED beyond; the host function has no such limit.  It
+ * runs on the null stream and has synchronised on return.  Transient device
+ * memory: 16 bytes per entry (sort keys and ids, double-buffered) and the
+ * radix sort's workspace, freed before it returns; SPMV_ERROR_OUT_OF_MEMORY
+ * leaves the outputs unspecified and leaks nothing. */
+int spmv_csr_transpose(int64_t m, int64_t n, int64_t nnz, const int64_t *row_ptr,
+                       const int32_t *col_idx, const double *val, int64_t *t_row_ptr,
+                       int32_t *t_col_idx, double *t_val, int64_t *perm);
+/* the same on `device` (-1: the current one), all arrays device memory there */
+int spmv_csr_transpose_device(int32_t device, int64_t m, int64_t n, int64_t nnz,
+                              const int64_t *d_row_ptr, const int32_t *d_col_idx,
+                              const double *d_val, int64_t *d_t_row_ptr,
+                              int32_t *d_t_col_idx, double *d_t_val, int64_t *d_perm);
+
+/* Plans of the transpose.  (m, n) is A's shape; the result is an ordinary plan
+ * of A^T: spmv_plan_info reports m = n_A and n = m_A, x holds m_A doubles and
+ * y holds n_A, and every array has the digest (spmv_plan_digest) of the plan
+ * spmv_plan_create_csr / _csr_device builds from spmv_csr_transpose's output
+ * with the same options.  execute, execute_alpha, execute_axpby,
+ * execute_multi, graphs, profile and digest treat it as any other plan.  It
+ * keeps neither A nor the permutation: device_bytes is its companion's.
+ *
+ * Host arrays follow opt->build as spmv_plan_create_csr does: the host
+ * transposition and the host builders (SPMV_BUILD_HOST, AUTO below 2^24
+ * entries), or the staging copy, the device transposition and the device
+ * builders; the device route falls back to the host route when the staging
+ * copy or the transposition's scratch does not fit, for what the device
+ * builders do not make, and from 2^31 - 1 entries on.  All routes give the
+ * same digests.  Device arrays: validated, transposed into scratch, built by
+ * the device builders, the scratch freed; transient memory is the CSR of A^T
+ * (12 bytes per entry + 8 (n + 1)) on top of the transposition's own, then of
+ * the builders'.  SPMV_ERROR_OUT_OF_MEMORY there is final (no host
+ * transposition from this entry point), as is SPMV_ERROR_NOT_SUPPORTED from
+ * 2^31 - 1 entries on.
+ *
+ * Value refresh: "the CSR the plan was created from" is A's.
+ * spmv_plan_update_prepare takes A's row_ptr (m_A + 1) and col_idx,
+ * spmv_plan_update_values takes values in A's entry order.
+ *
+ * Not covered: an op argument on spmv_execute* (A^T out of a plan of A), a
+ * plan that holds A and A^T together, a transposed spmv_plan_create_coo,
+ * spmv_dist_*, the drop-in (opt_hip.h) and the CSR5 handle. */
+int spmv_plan_create_csr_transposed(int64_t m, int64_t n, int64_t nnz, const int64_t *row_ptr,
+                                    const int32_t *col_idx, const double *val,
+                                    const spmv_options_t *opt, spmv_plan_t *plan);
+int spmv_plan_create_csr_device_transposed(int64_t m, int64_t n, int64_t nnz,
+                                           const int64_t *d_row_ptr, const int32_t *d_col_idx,
+                                           const double *d_val, const spmv_options_t *opt,
+                                           spmv_plan_t *plan);
+/* *transposed = 1 for a plan made by one of the two functions above, else 0 */
+int spmv_plan_is_transposed(spmv_plan_t plan, int32_t *transposed);
+
 int spmv_plan_destroy(spmv_plan_t plan);
 
 /* ---- per-phase profile (replaces the g_profile / PROF_BEGIN instrumentation
@@ -479,7 +560,12 @@ int spmv_axpby_path(spmv_plan_t plan, int32_t *fused);
  * "The CSR the plan was created from" is the (row_ptr, col_idx) handed to
  * spmv_plan_create_csr / _csr32 (row pointers widened) / _csr_device; for
  * spmv_plan_create_coo it is the sorted COO as passed: its entry order and
- * spmv_coo_to_csr's row pointers.
+ * spmv_coo_to_csr's row pointers.  For a plan of the transpose
+ * (spmv_plan_create_csr_transposed / _csr_device_transposed) it is A's:
+ * row_ptr has n + 1 entries in the plan's own (swapped) shape, and a pattern
+ * that fails spmv_plan_create_csr's input check for A's shape is refused with
+ * SPMV_ERROR_INVALID_VALUE like any wrong pattern.  (Prepare transposes the
+ * pattern on the device: SPMV_ERROR_NOT_SUPPORTED from 2^31 - 1 entries on.)
  *
  * In place.  No device pointer of the plan changes: HIP graphs created before
  * an update replay the new values, fused and generic multi executes see them,

@@ -113,6 +113,8 @@ EXPORTS = [
     "spmv_execute_multi", "spmv_time_multi", "spmv_multi_path",
     "spmv_plan_update_prepare", "spmv_plan_update_values",
     "spmv_execute_axpby", "spmv_time_axpby", "spmv_axpby_path",
+    "spmv_csr_transpose", "spmv_csr_transpose_device", "spmv_plan_create_csr_transposed",
+    "spmv_plan_create_csr_device_transposed", "spmv_plan_is_transposed",
 ]
 
 _lib = None
@@ -143,6 +145,12 @@ def lib():
     L.spmv_plan_create_csr32.argtypes = [i32, i32, i32, vp, vp, vp, C.POINTER(Options), C.POINTER(vp)]
     L.spmv_plan_create_csr_device.argtypes = [i64, i64, i64, vp, vp, vp, C.POINTER(Options),
                                               C.POINTER(vp)]
+    L.spmv_plan_create_csr_transposed.argtypes = [i64, i64, i64, vp, vp, vp, C.POINTER(Options), C.POINTER(vp)]
+    L.spmv_plan_create_csr_device_transposed.argtypes = [i64, i64, i64, vp, vp, vp, C.POINTER(Options),
+                                                         C.POINTER(vp)]
+    L.spmv_plan_is_transposed.argtypes = [vp, C.POINTER(i32)]
+    L.spmv_csr_transpose.argtypes = [i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.spmv_csr_transpose_device.argtypes = [i32, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]
     L.spmv_plan_destroy.argtypes = [vp]
     L.spmv_execute.argtypes = [vp, vp, vp, C.c_uint32]
     L.spmv_execute_alpha.argtypes = [vp, f64, vp, vp, C.c_uint32]
@@ -383,6 +391,51 @@ def coo_to_csr(m: int, row_idx: np.ndarray) -> np.ndarray:
     return rp
 
 
+def csr_transpose(m: int, n: int, row_ptr, col, val=None, perm: bool = False):
+    """The CSR of A^T from a CSR of A (m x n): (t_row_ptr [n + 1], t_col = the
+    source rows, t_val[, perm]).  Output row c holds A's entries of column c
+    in source order (a stable sort by column); values move as bits; perm is
+    the source entry of each output entry.  numpy arrays go to the host
+    function (spmv_csr_transpose), CUDA tensors to the device one
+    (spmv_csr_transpose_device), and the result is of the same kind.  val =
+    None: the pattern alone, t_val is None."""
+    L = lib()
+    if _is_device(row_ptr) or _is_device(col) or _is_device(val):
+        for name, t, dt in (("row_ptr", row_ptr, torch.int64), ("col", col, torch.int32),
+                            ("val", val, torch.float64)):
+            if t is None and name == "val":
+                continue
+            if not _is_device(t) or t.dtype != dt or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {dt} CUDA tensor")
+            if t.device != row_ptr.device:
+                raise ValueError(f"{name} is on {t.device}, row_ptr on {row_ptr.device}")
+        nnz = col.numel()
+        if row_ptr.numel() < m + 1 or (val is not None and val.numel() != nnz):
+            raise ValueError("row_ptr holds fewer than m + 1 entries, or val and col differ in length")
+        dev = row_ptr.device
+        t_rp = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        t_col = torch.empty(nnz, dtype=torch.int32, device=dev)
+        t_val = torch.empty(nnz, dtype=torch.float64, device=dev) if val is not None else None
+        pm = torch.empty(nnz, dtype=torch.int64, device=dev) if perm else None
+        _check(L.spmv_csr_transpose_device(dev.index or 0, m, n, nnz, _ptr(row_ptr), _ptr(col), _ptr(val),
+                                           _ptr(t_rp), _ptr(t_col), _ptr(t_val), _ptr(pm)),
+               "spmv_csr_transpose_device")
+    else:
+        row_ptr = np.ascontiguousarray(row_ptr, np.int64)
+        col = np.ascontiguousarray(col, np.int32)
+        val = None if val is None else np.ascontiguousarray(val, np.float64)
+        nnz = col.size
+        if row_ptr.size < m + 1 or (val is not None and val.size != nnz):
+            raise ValueError("row_ptr holds fewer than m + 1 entries, or val and col differ in length")
+        t_rp = np.empty(max(n, 0) + 1, np.int64)
+        t_col = np.empty(nnz, np.int32)
+        t_val = np.empty(nnz, np.float64) if val is not None else None
+        pm = np.empty(nnz, np.int64) if perm else None
+        _check(L.spmv_csr_transpose(m, n, nnz, _ptr(row_ptr), _ptr(col), _ptr(val), _ptr(t_rp), _ptr(t_col),
+                                    _ptr(t_val), _ptr(pm)), "spmv_csr_transpose")
+    return (t_rp, t_col, t_val, pm) if perm else (t_rp, t_col, t_val)
+
+
 # ---------------------------------------------------------------- plans
 def make_options(fmt="auto", device: int = -1, csr_lanes: int = 0, ell_width: int = 0,
                  ss_sigma: int = 0, dia_max_diags: int = 0, dia_max_fill: float = 0.0,
@@ -524,24 +577,30 @@ class Plan:
 
     # construction -------------------------------------------------------
     @classmethod
-    def from_csr(cls, m: int, n: int, row_ptr, col, val, fmt="auto", **opts) -> "Plan":
+    def from_csr(cls, m: int, n: int, row_ptr, col, val, fmt="auto", transpose: bool = False, **opts) -> "Plan":
+        """Plan from host arrays.  transpose=True: the plan of A^T
+        (spmv_plan_create_csr_transposed); (m, n) stays A's shape, the plan's
+        own is (n, m)."""
         rp = np.ascontiguousarray(row_ptr, np.int64)
         col = np.ascontiguousarray(col, np.int32)
         val = np.ascontiguousarray(val, np.float64)
         o = make_options(fmt, **opts)
         h = C.c_void_p()
-        _check(lib().spmv_plan_create_csr(m, n, len(val), rp.ctypes.data, col.ctypes.data,
-                                          val.ctypes.data, C.byref(o), C.byref(h)),
-               "spmv_plan_create_csr")
+        create = lib().spmv_plan_create_csr_transposed if transpose else lib().spmv_plan_create_csr
+        _check(create(m, n, len(val), rp.ctypes.data, col.ctypes.data, val.ctypes.data, C.byref(o), C.byref(h)),
+               "spmv_plan_create_csr_transposed" if transpose else "spmv_plan_create_csr")
         return cls(h.value)
 
     @classmethod
-    def from_device_csr(cls, m: int, n: int, row_ptr, col, val, fmt="auto", **opts) -> "Plan":
+    def from_device_csr(cls, m: int, n: int, row_ptr, col, val, fmt="auto", transpose: bool = False,
+                        **opts) -> "Plan":
         """Plan from torch CUDA tensors (int64 row_ptr, int32 col, float64
         val): every format is built on the device, AUTO resolved there
         (spmv_plan_create_csr_device).  The one exception: BIN rows out of
         strip order when the device has no room for their sorted copy are
-        copied to the host and built by the host builders (same layout)."""
+        copied to the host and built by the host builders (same layout).
+        transpose=True: the plan of A^T, from a CSR of A^T made on the device
+        (spmv_plan_create_csr_device_transposed); (m, n) stays A's shape."""
         for name, t, dt in (("row_ptr", row_ptr, torch.int64), ("col", col, torch.int32),
                             ("val", val, torch.float64)):
             if not _is_device(t) or t.dtype != dt or not t.is_contiguous():
@@ -550,9 +609,9 @@ class Plan:
             opts["device"] = row_ptr.device.index or 0
         o = make_options(fmt, **opts)
         h = C.c_void_p()
-        _check(lib().spmv_plan_create_csr_device(m, n, val.numel(), _ptr(row_ptr), _ptr(col), _ptr(val),
-                                                 C.byref(o), C.byref(h)),
-               "spmv_plan_create_csr_device")
+        create = lib().spmv_plan_create_csr_device_transposed if transpose else lib().spmv_plan_create_csr_device
+        _check(create(m, n, val.numel(), _ptr(row_ptr), _ptr(col), _ptr(val), C.byref(o), C.byref(h)),
+               "spmv_plan_create_csr_device_transposed" if transpose else "spmv_plan_create_csr_device")
         return cls(h.value)
 
     @classmethod
@@ -662,10 +721,13 @@ class Plan:
         """Teach the plan where every entry of the CSR it was created from
         lives in its layout (spmv_plan_update_prepare; about one plan build,
         once).  row_ptr / col: the pattern the plan was built from, as numpy
-        arrays (like from_csr) or CUDA tensors (like from_device_csr)."""
+        arrays (like from_csr) or CUDA tensors (like from_device_csr).  For a
+        plan of the transpose that CSR is A's: row_ptr holds n + 1 entries in
+        the plan's own shape."""
         nnz = self.info()["nnz"]
+        src_m = self.n if self.transposed else self.m
         if _is_device(row_ptr) or _is_device(col):
-            for name, t, dt, need in (("row_ptr", row_ptr, torch.int64, self.m + 1), ("col", col, torch.int32, nnz)):
+            for name, t, dt, need in (("row_ptr", row_ptr, torch.int64, src_m + 1), ("col", col, torch.int32, nnz)):
                 if not _is_device(t) or t.dtype != dt or not t.is_contiguous():
                     raise ValueError(f"{name} must be a contiguous {dt} CUDA tensor")
                 if t.device.index != self.device:
@@ -676,9 +738,9 @@ class Plan:
         else:
             row_ptr = np.ascontiguousarray(row_ptr, np.int64)
             col = np.ascontiguousarray(col, np.int32)
-            if row_ptr.size < self.m + 1 or col.size < nnz:
+            if row_ptr.size < src_m + 1 or col.size < nnz:
                 raise ValueError(f"row_ptr / col hold {row_ptr.size} / {col.size} entries, "
-                                 f"the plan needs {self.m + 1} / {nnz}")
+                                 f"the plan needs {src_m + 1} / {nnz}")
             flags = 0
         _check(lib().spmv_plan_update_prepare(self._h, _ptr(row_ptr), _ptr(col), flags), "spmv_plan_update_prepare")
 
@@ -744,6 +806,14 @@ class Plan:
         i = PlanInfo()
         _check(lib().spmv_plan_info(self._h, C.byref(i)), "spmv_plan_info")
         return i.as_dict()
+
+    @property
+    def transposed(self) -> bool:
+        """True for a plan of the transpose (from_csr / from_device_csr with
+        transpose=True): m, n and the x / y lengths are A^T's."""
+        v = C.c_int32()
+        _check(lib().spmv_plan_is_transposed(self._h, C.byref(v)), "spmv_plan_is_transposed")
+        return bool(v.value)
 
     def built_on_device(self) -> bool:
         """True when the layout was built in HBM (spmv_plan_built_on_device)."""

@@ -1,6 +1,6 @@
 // build_util.hpp -- plumbing shared by the plan builders (formats.cpp,
 // build_bin.cpp, k_convert.hip, k_devbuild.hip, k_css_build.hip,
-// k_bin_build.hip): transient device scratch, plan allocations and uploads,
+// k_bin_build.hip, k_transpose.hip): transient device scratch, plan allocations and uploads,
 // launch grids and the end-of-phase check.  Host code only.
 #pragma once
 
@@ -41,6 +41,13 @@ struct DevScratch {
         return SPMV_SUCCESS;
     }
 };
+
+// k_bin_build.hip: stable radix sort of (key, value) pairs by the keys' low
+// `bits` bits on sc.st, double-buffered: keys[0] / vals[0] hold the input,
+// keys[*current] / vals[*current] the result (bits = 0: the input itself), the
+// other pair is clobbered.  The workspace lives in sc.
+int sort_pairs_u32(DevScratch &sc, uint32_t *const keys[2], uint32_t *const vals[2], int64_t count, int bits,
+                   int *current);
 
 // count elements owned by the plan (zero-count safe)
 template <typename T>

@@ -110,12 +110,13 @@ static void keep_options(spmv_plan_s *p, const spmv_options_t &o, int fmt, int d
 
 // Validate a host CSR before anything touches the GPU: an out-of-range
 // column would become an out-of-bounds gather on the device.
-static int validate_csr(const HostCsr &A) {
+// (need_val = false: a pattern, spmv_csr_transpose without values)
+static int validate_csr(const HostCsr &A, bool need_val = true) {
     SPMV_CHECK_ARG(A.m >= 0 && A.n >= 0 && A.nnz >= 0, "negative dimension");
     SPMV_CHECK_ARG(A.m < (int64_t)INT32_MAX && A.n < (int64_t)INT32_MAX,
                    "m and n must be < 2^31 (int32 column indices)");
     SPMV_CHECK_ARG(A.row_ptr != nullptr, "row_ptr is NULL");
-    SPMV_CHECK_ARG(A.nnz == 0 || (A.col != nullptr && A.val != nullptr), "col/val is NULL");
+    SPMV_CHECK_ARG(A.nnz == 0 || (A.col != nullptr && (A.val != nullptr || !need_val)), "col/val is NULL");
     SPMV_CHECK_ARG(A.row_ptr[0] == 0, "row_ptr[0] != 0");
     SPMV_CHECK_ARG(A.row_ptr[A.m] == A.nnz, "row_ptr[m] != nnz");
     int64_t bad_rp = 0, bad_col = 0;
@@ -126,6 +127,40 @@ static int validate_csr(const HostCsr &A) {
 #pragma omp parallel for schedule(static) reduction(+ : bad_col)
     for (int64_t j = 0; j < A.nnz; ++j) bad_col += (A.col[j] < 0) | (A.col[j] >= n);
     SPMV_CHECK_ARG(bad_col == 0, "column index outside [0, n)");
+    return SPMV_SUCCESS;
+}
+
+// The CSR of A^T from a validated host CSR of A: a stable counting sort of
+// the entries by column (output row c = A's entries of column c in ascending
+// entry index), t_col = the source rows.  The reference of
+// transpose_csr_device (k_transpose.hip), byte for byte.  t_val and perm are
+// optional; values move as 64-bit words.
+static void transpose_csr_host(const HostCsr &A, int64_t *t_rp, int32_t *t_col, double *t_val, int64_t *perm) {
+    std::fill(t_rp, t_rp + A.n + 1, (int64_t)0);
+    for (int64_t j = 0; j < A.nnz; ++j) ++t_rp[A.col[j] + 1];
+    for (int64_t c = 0; c < A.n; ++c) t_rp[c + 1] += t_rp[c];
+    // t_rp[c] is column c's cursor while the entries are placed, then shifted back
+    for (int64_t r = 0; r < A.m; ++r)
+        for (int64_t j = A.row_ptr[r]; j < A.row_ptr[r + 1]; ++j) {
+            const int64_t d = t_rp[A.col[j]]++;
+            t_col[d] = (int32_t)r;
+            if (t_val) std::memcpy(&t_val[d], &A.val[j], sizeof(double));
+            if (perm) perm[d] = j;
+        }
+    for (int64_t c = A.n; c > 0; --c) t_rp[c] = t_rp[c - 1];
+    t_rp[0] = 0;
+}
+
+// every pointer device memory on `dev`?
+static int check_device_arrays(const void *const *ptrs, int count, int dev, const char *who) {
+    for (int k = 0; k < count; ++k) {
+        hipPointerAttribute_t a;
+        if (hipPointerGetAttributes(&a, ptrs[k]) != hipSuccess || a.type != hipMemoryTypeDevice || a.device != dev) {
+            (void)hipGetLastError();
+            set_error(std::string(who) + ": arrays must be device memory on the plan's device");
+            return SPMV_ERROR_INVALID_VALUE;
+        }
+    }
     return SPMV_SUCCESS;
 }
 
@@ -158,14 +193,7 @@ static int create_device_impl(int64_t m, int64_t n, int64_t nnz, const int64_t *
     int dev = -1;
     SPMV_RETURN_IF(open_device(o.device, &dev));
     const void *ptrs[3] = {d_row_ptr, d_col_idx, d_val};
-    for (int k = 0; k < (nnz ? 3 : 1); ++k) {
-        hipPointerAttribute_t a;
-        if (hipPointerGetAttributes(&a, ptrs[k]) != hipSuccess || a.type != hipMemoryTypeDevice || a.device != dev) {
-            (void)hipGetLastError();
-            set_error("spmv_plan_create_csr_device: arrays must be device memory on the plan's device");
-            return SPMV_ERROR_INVALID_VALUE;
-        }
-    }
+    SPMV_RETURN_IF(check_device_arrays(ptrs, nnz ? 3 : 1, dev, "spmv_plan_create_csr_device"));
     SPMV_RETURN_IF(validate_csr_device(d_row_ptr, m, d_col_idx, nnz, n));
     spmv_plan_s *p = new_plan(dev, m, n, nnz);
     if (!p) return SPMV_ERROR_OUT_OF_MEMORY;
@@ -258,14 +286,35 @@ static int create_device_impl(int64_t m, int64_t n, int64_t nnz, const int64_t *
     }
 }
 
+// The plan of A^T from a validated CSR of A in HBM on the bound device: the
+// CSR of A^T in scratch (k_transpose.hip, its sort buffers freed before the
+// builders run), create_device_impl on it, the scratch freed.  The plan keeps
+// neither A nor the permutation.
+static int create_device_transposed_impl(int64_t m, int64_t n, int64_t nnz, const int64_t *d_row_ptr,
+                                         const int32_t *d_col_idx, const double *d_val, const spmv_options_t *opt,
+                                         spmv_plan_t *out, spmv_options_t *need_host) {
+    DevScratch scratch(nullptr);
+    int64_t *t_rp = nullptr;
+    int32_t *t_col = nullptr;
+    double *t_val = nullptr;
+    SPMV_RETURN_IF(scratch.alloc(&t_rp, (size_t)n + 1, "transposed row_ptr"));
+    SPMV_RETURN_IF(scratch.alloc(&t_col, (size_t)nnz, "transposed col_idx"));
+    SPMV_RETURN_IF(scratch.alloc(&t_val, (size_t)nnz, "transposed val"));
+    SPMV_RETURN_IF(transpose_csr_device(m, n, nnz, d_row_ptr, d_col_idx, d_val, t_rp, t_col, t_val, nullptr));
+    const int st = create_device_impl(n, m, nnz, t_rp, t_col, t_val, opt, out, need_host);
+    if (st == SPMV_SUCCESS) (*out)->transposed = 1;
+    return st;
+}
+
 // Stage a (validated) host CSR into HBM and build the plan there
 // (create_device_impl: the same layouts byte for byte, AUTO resolved by the
-// same chooser).  A format the device builders do not make comes back as
+// same chooser; transpose: the plan of A^T, create_device_transposed_impl).
+// A format the device builders do not make comes back as
 // kNeedHostBuild with the resolved options in *host_opts;
-// SPMV_ERROR_OUT_OF_MEMORY when the staging copy does not fit.  Either way
-// the caller then takes the host builders.
+// SPMV_ERROR_OUT_OF_MEMORY when the staging copy (or the transposition's
+// scratch) does not fit.  Either way the caller then takes the host builders.
 static int create_via_device(const HostCsr &A, spmv_options_t o, int dev, spmv_plan_t *out,
-                             spmv_options_t *host_opts) {
+                             spmv_options_t *host_opts, bool transpose = false) {
     void *d[3] = {nullptr, nullptr, nullptr};
     const size_t bytes[3] = {8 * (size_t)(A.m + 1), 4 * (size_t)std::max<int64_t>(A.nnz, 1),
                              8 * (size_t)std::max<int64_t>(A.nnz, 1)};
@@ -291,9 +340,50 @@ static int create_via_device(const HostCsr &A, spmv_options_t o, int dev, spmv_p
         return SPMV_ERROR_HIP;
     }
     o.device = dev;
-    const int st = create_device_impl(A.m, A.n, A.nnz, (const int64_t *)d[0], (const int32_t *)d[1],
-                                      (const double *)d[2], &o, out, host_opts);
+    const int st = (transpose ? create_device_transposed_impl : create_device_impl)(
+        A.m, A.n, A.nnz, (const int64_t *)d[0], (const int32_t *)d[1], (const double *)d[2], &o, out, host_opts);
     release();
+    return st;
+}
+
+// spmv_plan_create_csr_transposed's body: create_from_csr's routing with the
+// transposition in front of the builders of either route.
+static int create_from_csr_transposed(const HostCsr &A, const spmv_options_t *opt_in, spmv_plan_t *out) {
+    SPMV_CHECK_ARG(out != nullptr, "plan out-pointer is NULL");
+    *out = nullptr;
+    spmv_options_t o;
+    if (opt_in) o = *opt_in;
+    else spmv_options_default(&o);
+    SPMV_CHECK_ARG(o.build >= SPMV_BUILD_AUTO && o.build <= SPMV_BUILD_DEVICE, "build must be SPMV_BUILD_*");
+    SPMV_RETURN_IF(validate_csr(A));
+    int dev = -1;
+    SPMV_RETURN_IF(open_device(o.device, &dev));
+    // (the device transposition's 32-bit entry ids: larger matrices take the host route)
+    if ((o.build == SPMV_BUILD_DEVICE || (o.build == SPMV_BUILD_AUTO && A.nnz >= kDeviceBuildMinNnz)) &&
+        A.nnz < (int64_t)INT32_MAX) {
+        spmv_options_t ho = o;
+        const int st = create_via_device(A, o, dev, out, &ho, true);
+        if (st != SPMV_ERROR_OUT_OF_MEMORY && st != kNeedHostBuild) return st;
+        if (st == kNeedHostBuild) o = ho;
+        SPMV_HIP_TRY(hipSetDevice(dev));
+    }
+    std::vector<int64_t> t_rp;
+    std::vector<int32_t> t_col;
+    std::vector<double> t_val;
+    try {
+        t_rp.resize((size_t)A.n + 1);
+        t_col.resize((size_t)A.nnz);
+        t_val.resize((size_t)A.nnz);
+    } catch (const std::bad_alloc &) {
+        set_error("host allocation of the transposed CSR failed");
+        return SPMV_ERROR_OUT_OF_MEMORY;
+    }
+    transpose_csr_host(A, t_rp.data(), t_col.data(), t_val.data(), nullptr);
+    o.device = dev;
+    o.build = SPMV_BUILD_HOST;
+    const HostCsr T{A.n, A.m, A.nnz, t_rp.data(), t_col.data(), t_val.data()};
+    const int st = create_from_csr(T, &o, out);
+    if (st == SPMV_SUCCESS) (*out)->transposed = 1;
     return st;
 }
 
@@ -440,6 +530,73 @@ int spmv_plan_create_csr32_device(int32_t m, int32_t n, int32_t nnz, const int32
     const int st = spmv_plan_create_csr_device(m, n, nnz, rp64, d_col_idx, d_val, opt, out);
     (void)hipFree(rp64);
     return st;
+}
+
+// ---- the transpose: the CSR of A^T, and plans built from it -----------------
+int spmv_csr_transpose(int64_t m, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col_idx,
+                       const double *val, int64_t *t_row_ptr, int32_t *t_col_idx, double *t_val, int64_t *perm) {
+    SPMV_CHECK_ARG((val == nullptr) == (t_val == nullptr) || nnz <= 0, "val and t_val: both or neither");
+    SPMV_CHECK_ARG(t_row_ptr != nullptr && (nnz <= 0 || t_col_idx != nullptr), "t_row_ptr / t_col_idx is NULL");
+    const HostCsr A{m, n, nnz, row_ptr, col_idx, val};
+    SPMV_RETURN_IF(validate_csr(A, false));
+    transpose_csr_host(A, t_row_ptr, t_col_idx, t_val, perm);
+    return SPMV_SUCCESS;
+}
+
+int spmv_csr_transpose_device(int32_t device, int64_t m, int64_t n, int64_t nnz, const int64_t *d_row_ptr,
+                              const int32_t *d_col_idx, const double *d_val, int64_t *d_t_row_ptr,
+                              int32_t *d_t_col_idx, double *d_t_val, int64_t *d_perm) {
+    SPMV_CHECK_ARG((d_val == nullptr) == (d_t_val == nullptr) || nnz <= 0, "val and t_val: both or neither");
+    SPMV_CHECK_ARG(d_t_row_ptr != nullptr && (nnz <= 0 || d_t_col_idx != nullptr), "t_row_ptr / t_col_idx is NULL");
+    SPMV_CHECK_ARG(m >= 0 && n >= 0 && nnz >= 0, "negative dimension");
+    SPMV_CHECK_ARG(m < (int64_t)INT32_MAX && n < (int64_t)INT32_MAX, "m and n must be < 2^31 (int32 column indices)");
+    SPMV_CHECK_ARG(d_row_ptr != nullptr, "row_ptr is NULL");
+    SPMV_CHECK_ARG(nnz == 0 || d_col_idx != nullptr, "col_idx is NULL");
+    int dev = -1;
+    SPMV_RETURN_IF(open_device(device, &dev));
+    std::vector<const void *> ptrs = {d_row_ptr, d_t_row_ptr};
+    if (nnz) {
+        ptrs.insert(ptrs.end(), {d_col_idx, d_t_col_idx});
+        if (d_val) ptrs.insert(ptrs.end(), {d_val, d_t_val});
+        if (d_perm) ptrs.push_back(d_perm);
+    }
+    SPMV_RETURN_IF(check_device_arrays(ptrs.data(), (int)ptrs.size(), dev, "spmv_csr_transpose_device"));
+    SPMV_RETURN_IF(validate_csr_device(d_row_ptr, m, d_col_idx, nnz, n));
+    return transpose_csr_device(m, n, nnz, d_row_ptr, d_col_idx, d_val, d_t_row_ptr, d_t_col_idx, d_t_val, d_perm);
+}
+
+int spmv_plan_create_csr_transposed(int64_t m, int64_t n, int64_t nnz, const int64_t *row_ptr,
+                                    const int32_t *col_idx, const double *val, const spmv_options_t *opt,
+                                    spmv_plan_t *plan) {
+    const HostCsr A{m, n, nnz, row_ptr, col_idx, val};
+    return create_from_csr_transposed(A, opt, plan);
+}
+
+int spmv_plan_create_csr_device_transposed(int64_t m, int64_t n, int64_t nnz, const int64_t *d_row_ptr,
+                                           const int32_t *d_col_idx, const double *d_val, const spmv_options_t *opt,
+                                           spmv_plan_t *out) {
+    SPMV_CHECK_ARG(out != nullptr, "plan out-pointer is NULL");
+    *out = nullptr;
+    SPMV_CHECK_ARG(m >= 0 && n >= 0 && nnz >= 0, "negative dimension");
+    SPMV_CHECK_ARG(m < (int64_t)INT32_MAX && n < (int64_t)INT32_MAX, "m and n must be < 2^31 (int32 column indices)");
+    SPMV_CHECK_ARG(d_row_ptr != nullptr, "row_ptr is NULL");
+    SPMV_CHECK_ARG(nnz == 0 || (d_col_idx != nullptr && d_val != nullptr), "col/val is NULL");
+    int dev = -1;
+    SPMV_RETURN_IF(open_device(opt ? opt->device : -1, &dev));
+    const void *ptrs[3] = {d_row_ptr, d_col_idx, d_val};
+    SPMV_RETURN_IF(check_device_arrays(ptrs, nnz ? 3 : 1, dev, "spmv_plan_create_csr_device_transposed"));
+    SPMV_RETURN_IF(validate_csr_device(d_row_ptr, m, d_col_idx, nnz, n));
+    spmv_options_t o;
+    if (opt) o = *opt;
+    else spmv_options_default(&o);
+    o.device = dev;
+    return create_device_transposed_impl(m, n, nnz, d_row_ptr, d_col_idx, d_val, &o, out, nullptr);
+}
+
+int spmv_plan_is_transposed(spmv_plan_t p, int32_t *transposed) {
+    SPMV_CHECK_ARG(p != nullptr && transposed != nullptr, "NULL plan or out-pointer");
+    *transposed = p->transposed;
+    return SPMV_SUCCESS;
 }
 
 int spmv_coo_to_csr(int32_t m, int64_t nnz, const int32_t *row_idx, int64_t *row_ptr) {
@@ -881,15 +1038,17 @@ int spmv_plan_update_prepare(spmv_plan_t p, const int64_t *row_ptr, const int32_
     SPMV_RETURN_IF(bind_device(p));
     // the pattern in HBM (a host pattern is staged, as create_via_device does)
     // with values 1 .. nnz; the builders run on the null stream
+    // (a plan of the transpose was created from A: the source has p->n rows)
+    const int64_t src_m = p->transposed ? p->n : p->m;
     DevScratch scratch(nullptr);
     const int64_t *d_rp = row_ptr;
     const int32_t *d_col = col_idx;
     if (!(flags & SPMV_CSR_DEVICE)) {
         int64_t *rp = nullptr;
         int32_t *col = nullptr;
-        SPMV_RETURN_IF(scratch.alloc(&rp, (size_t)p->m + 1, "row_ptr staging"));
+        SPMV_RETURN_IF(scratch.alloc(&rp, (size_t)src_m + 1, "row_ptr staging"));
         SPMV_RETURN_IF(scratch.alloc(&col, (size_t)p->nnz, "col_idx staging"));
-        SPMV_HIP_TRY(hipMemcpy(rp, row_ptr, 8 * (size_t)(p->m + 1), hipMemcpyHostToDevice));
+        SPMV_HIP_TRY(hipMemcpy(rp, row_ptr, 8 * (size_t)(src_m + 1), hipMemcpyHostToDevice));
         SPMV_HIP_TRY(hipMemcpy(col, col_idx, 4 * (size_t)p->nnz, hipMemcpyHostToDevice));
         d_rp = rp;
         d_col = col;
@@ -897,6 +1056,23 @@ int spmv_plan_update_prepare(spmv_plan_t p, const int64_t *row_ptr, const int32_
     double *d_val = nullptr;
     SPMV_RETURN_IF(scratch.alloc(&d_val, (size_t)p->nnz, "shadow values"));
     SPMV_RETURN_IF(launch_iota_values(nullptr, d_val, p->nnz));
+    if (p->transposed) {
+        // A's pattern with the values 1 .. nnz, transposed: the shadow's
+        // values then name A's entries, and the maps point into A's order
+        const void *ptrs[2] = {d_rp, d_col};
+        SPMV_RETURN_IF(check_device_arrays(ptrs, 2, p->device, "spmv_plan_update_prepare"));
+        SPMV_RETURN_IF(validate_csr_device(d_rp, src_m, d_col, p->nnz, p->m));
+        int64_t *t_rp = nullptr;
+        int32_t *t_col = nullptr;
+        double *t_val = nullptr;
+        SPMV_RETURN_IF(scratch.alloc(&t_rp, (size_t)p->m + 1, "transposed row_ptr"));
+        SPMV_RETURN_IF(scratch.alloc(&t_col, (size_t)p->nnz, "transposed col_idx"));
+        SPMV_RETURN_IF(scratch.alloc(&t_val, (size_t)p->nnz, "transposed shadow values"));
+        SPMV_RETURN_IF(transpose_csr_device(src_m, p->m, p->nnz, d_rp, d_col, d_val, t_rp, t_col, t_val, nullptr));
+        d_rp = t_rp;
+        d_col = t_col;
+        d_val = t_val;
+    }
     // the shadow: the plan's resolved options, no placement search, no VMM
     spmv_options_t o = p->opts;
     o.placement = SPMV_PLACEMENT_PLAIN;

@@ -445,6 +445,7 @@ struct spmv_plan_s {
     int format = SPMV_FORMAT_CSR;
     int device = 0;
     int built_on_device = 0;  // 1: the layout was built in HBM (spmv_plan_create_csr_device or build AUTO/DEVICE)
+    int transposed = 0;       // 1: a plan of the transpose (spmv_plan_create_csr*_transposed): m, n are A^T's
     int64_t m = 0, n = 0, nnz = 0;
     hipStream_t stream = nullptr;
     // the options the plan was built with, resolved: format = the one built
@@ -578,6 +579,13 @@ int bin_long_fill_device(spmv_plan_s *p, const DevCsr &A, const BinLayout &L, co
 int validate_csr_device(const int64_t *d_rp, int64_t m, const int32_t *d_col, int64_t nnz, int64_t n);
 int widen_row_ptr_device(const int32_t *d_rp32, int64_t m, int64_t **d_rp64);  // hipMalloc'd; caller frees
 int launch_scale(const spmv_plan_s *p, double *y, double alpha);              // y *= alpha on p->stream
+// k_transpose.hip -- the CSR of A^T (n rows) from a validated device CSR of A:
+// entries stably sorted by column, t_col = source rows; d_val / d_t_val both
+// null: pattern only; d_perm (source entry of each output entry) optional.
+// Null stream, synchronised on return, scratch freed.  NOT_SUPPORTED from
+// nnz = 2^31 - 1 on.
+int transpose_csr_device(int64_t m, int64_t n, int64_t nnz, const int64_t *d_rp, const int32_t *d_col,
+                         const double *d_val, int64_t *d_t_rp, int32_t *d_t_col, double *d_t_val, int64_t *d_perm);
 int build_csr_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o);
 int build_ss_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o);
 int choose_format(const HostCsr &A, const spmv_options_t &o);

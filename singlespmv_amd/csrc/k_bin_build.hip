@@ -493,4 +493,22 @@ int bin_sort_rows_device(spmv_plan_s *p, const DevCsr &A, int32_t *col2, double 
     return bin_sort_rows_t<uint64_t>(p, A, col2, val2);
 }
 
+// The (uint32 key, uint32 value) radix sort of bin_sort_place, for
+// k_transpose.hip: hipCUB's kernels are instantiated per translation unit, so
+// the transposition sorts through this one and adds none to the library.
+int sort_pairs_u32(DevScratch &sc, uint32_t *const keys[2], uint32_t *const vals[2], const int64_t count, int bits,
+                   int *current) {
+    const hipStream_t st = sc.st;
+    hipcub::DoubleBuffer<uint32_t> dk(keys[0], keys[1]), dv(vals[0], vals[1]);
+    *current = 0;
+    if (bits <= 0 || count <= 0) return SPMV_SUCCESS;  // nothing to order by: no pass runs
+    size_t tb = 0;
+    SPMV_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dk, dv, count, 0, bits, st));
+    char *tmp = nullptr;
+    SPMV_RETURN_IF(sc.alloc(&tmp, tb, "sort workspace"));
+    SPMV_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, dk, dv, count, 0, bits, st));
+    *current = dk.selector;  // (dv's is the same)
+    return SPMV_SUCCESS;
+}
+
 }  // namespace spmv
