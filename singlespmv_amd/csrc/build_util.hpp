@@ -15,7 +15,7 @@ namespace spmv {
 // Transient device scratch of a builder, freed on every exit path once the
 // stream its kernels run on has drained.  Allocations go through
 // scratch_malloc (internal.hpp): OUT_OF_MEMORY only for hipErrorOutOfMemory
-// (the host-CSR routing of capi.cpp then takes the host builders), HIP's
+// (the host-CSR routing of capi_create.cpp then takes the host builders), HIP's
 // sticky error cleared.
 struct DevScratch {
     hipStream_t st;

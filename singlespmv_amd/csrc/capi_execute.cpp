@@ -1,0 +1,546 @@
+// capi_execute.cpp -- the per-call side of include/spmv_hip.h: execute (one
+// vector, k vectors, alpha and beta), timing, graphs, the phase profile.
+// Every entry point returns an int status.
+#include <algorithm>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "build_util.hpp"
+
+namespace spmv {
+
+static int dispatch(const spmv_plan_s *p, const double *x, double *y) {
+    switch (p->format) {
+        case SPMV_FORMAT_CSR: return launch_csr(p, x, y);
+        case SPMV_FORMAT_ELL: return launch_ell(p, x, y);
+        case SPMV_FORMAT_HYB:
+        case SPMV_FORMAT_JDS:
+            SPMV_RETURN_IF(launch_ell(p, x, y));
+            phase_mark(p);  // ell | overflow
+            return launch_hyb_overflow(p, x, y);
+        case SPMV_FORMAT_SS: return launch_ss(p, x, y);
+        case SPMV_FORMAT_DIA: return launch_dia(p, x, y);
+        case SPMV_FORMAT_CSS: return launch_css(p, x, y);
+        case SPMV_FORMAT_COO: return launch_coo(p, x, y);
+        case SPMV_FORMAT_BIN: return launch_bin(p, x, y);
+    }
+    set_error("plan has an unknown format");
+    return SPMV_ERROR_INVALID_VALUE;
+}
+
+int bind_device(const spmv_plan_s *p) {
+    int cur = -1;
+    SPMV_HIP_TRY(hipGetDevice(&cur));
+    if (cur != p->device) SPMV_HIP_TRY(hipSetDevice(p->device));
+    return SPMV_SUCCESS;
+}
+
+// Times `iters` repetitions of `run` (a status; the first failure ends the
+// loop) between two events on `s`.  Both events are destroyed on every path.
+template <class Run>
+static int time_on_stream(hipStream_t s, int32_t iters, double *ms, Run run) {
+    hipEvent_t a = nullptr, b = nullptr;
+    hipError_t e = hipEventCreate(&a);
+    if (e == hipSuccess) e = hipEventCreate(&b);
+    if (e == hipSuccess) e = hipEventRecord(a, s);
+    int st = SPMV_SUCCESS;
+    for (int32_t i = 0; i < iters && st == SPMV_SUCCESS && e == hipSuccess; ++i) st = run();
+    if (e == hipSuccess) e = hipEventRecord(b, s);
+    if (e == hipSuccess) e = hipEventSynchronize(b);
+    float f = 0;
+    if (e == hipSuccess) e = hipEventElapsedTime(&f, a, b);
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+    SPMV_HIP_TRY(e);
+    *ms = f;
+    return st;
+}
+
+// the staging vector *buf of the plan (x_stage, y_stage: `count` doubles),
+// allocated at the first use
+static int ensure_stage(spmv_plan_s *p, double **buf, int64_t count) {
+    return *buf ? SPMV_SUCCESS : plan_alloc(p, buf, count);
+}
+
+// How every execute ends, once the copy of a host y is queued: a host y is
+// waited for; a device y too, unless the call is SPMV_ASYNC and x was on the
+// device as well (a host x must be free to change on return).
+static int finish_execute(const spmv_plan_s *p, uint32_t flags, bool host_y) {
+    if (host_y || !(flags & SPMV_ASYNC) || !(flags & SPMV_X_DEVICE)) SPMV_HIP_TRY(hipStreamSynchronize(p->stream));
+    return SPMV_SUCCESS;
+}
+
+// JDS without overflow rows: the sliced-ELL part alone, one writer per row.
+// (With overflow rows a second kernel adds into the y the ELL part wrote.)
+static bool jds_without_overflow(const spmv_plan_s *p) {
+    return p->format == SPMV_FORMAT_JDS && p->hyb.nnz == 0 && p->hyb.n_rows == 0;
+}
+
+// ---- y = alpha * A x + beta * y (epilogues: k_csr / k_ell / k_dia.hip; second pass: k_axpby.hip) --
+
+// One writer per row: CSR (every kernel), ELL, DIA, and JDS without overflow
+// rows take alpha and beta in the store epilogue.  Every other plan runs its
+// own kernels into a scratch vector and one axpby pass.
+static bool axpby_fused(const spmv_plan_s *p) {
+    // probe build: the generic route forced on any plan (tools/axpby_times.py)
+    if (const char *e = probe_env("SPMV_LAUNCH_AXPBY_GENERIC"))
+        if (std::atoi(e) != 0) return false;
+    if (p->format == SPMV_FORMAT_CSR || p->format == SPMV_FORMAT_ELL || p->format == SPMV_FORMAT_DIA) return true;
+    return jds_without_overflow(p);
+}
+
+// the generic path's row sums (beta != 0 on a plan that is not fused): m + 2
+// doubles of plain hipMalloc memory (COO adds into them with f64 atomics),
+// allocated at the first use.  The spare doubles let t start at y's alignment
+// modulo 16 (k_axpby.hip).
+static int axpby_scratch(spmv_plan_s *p, double beta) {
+    if (beta == 0.0 || p->m == 0 || axpby_fused(p) || p->ab_scratch) return SPMV_SUCCESS;
+    void *q = nullptr;
+    SPMV_RETURN_IF(p->arena.alloc_plain(&q, sizeof(double) * (size_t)(p->m + 2)));
+    p->ab_scratch = (double *)q;
+    return SPMV_SUCCESS;
+}
+
+// the launches of y = alpha * A x + beta * y on device x and y, on p->stream.
+// beta = 0 (either sign): y is never read; A x, then the scale by alpha.
+static int axpby_dispatch(spmv_plan_s *p, const Axpby &ab, const double *x, double *y) {
+    if (ab.beta == 0.0) {
+        SPMV_RETURN_IF(dispatch(p, x, y));
+        return launch_scale(p, y, ab.alpha);
+    }
+    if (p->m == 0) return SPMV_SUCCESS;
+    if (axpby_fused(p)) {
+        switch (p->format) {
+            case SPMV_FORMAT_CSR: return launch_csr(p, x, y, &ab);
+            case SPMV_FORMAT_DIA: return launch_dia(p, x, y, &ab);
+            default: return launch_ell(p, x, y, &ab);  // ELL, JDS without overflow rows
+        }
+    }
+    SPMV_RETURN_IF(axpby_scratch(p, ab.beta));
+    double *t = p->ab_scratch + ((reinterpret_cast<uintptr_t>(y) >> 3) & 1);
+    SPMV_RETURN_IF(dispatch(p, x, t));
+    return launch_axpby(p, y, t, ab);
+}
+
+// The body of spmv_execute, spmv_execute_alpha (beta = 0) and
+// spmv_execute_axpby: the flag rules of each, x and y staged where they are
+// host memory, the launches, the copy back.
+static int execute_impl(spmv_plan_t p, const Axpby &ab, const double *x, double *y, uint32_t flags, bool axpby) {
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    const bool staged = (flags & SPMV_X_STAGED) != 0;
+    const bool y_staged = !axpby && (flags & SPMV_Y_STAGED) != 0;
+    SPMV_CHECK_ARG((x != nullptr || p->n == 0 || staged) && (y != nullptr || p->m == 0 || y_staged),
+                   "x or y is NULL");
+    if (axpby) {
+        SPMV_CHECK_ARG(!(flags & ~(SPMV_X_DEVICE | SPMV_Y_DEVICE | SPMV_ASYNC | SPMV_X_STAGED | SPMV_Y_STAGED)),
+                       "spmv_execute_axpby: unknown flag bits");
+        SPMV_CHECK_ARG(!(flags & SPMV_Y_STAGED), "spmv_execute_axpby: SPMV_Y_STAGED is not supported (y is an input)");
+    } else {
+        SPMV_CHECK_ARG(!(y_staged && (flags & SPMV_Y_DEVICE)), "SPMV_Y_STAGED with SPMV_Y_DEVICE");
+    }
+    SPMV_CHECK_ARG(!staged || p->x_stage != nullptr, "SPMV_X_STAGED without a previously staged x");
+    SPMV_RETURN_IF(bind_device(p));
+    // spmv_fetch_y serves the y of the latest execute only when that execute
+    // was SPMV_Y_STAGED: any other execute (device y, host y) clears the mark
+    p->y_staged = false;
+    const bool x_host = !staged && !(flags & SPMV_X_DEVICE);
+    const bool y_dev = (flags & SPMV_Y_DEVICE) != 0;
+    if (staged) flags |= SPMV_X_DEVICE;
+    // every allocation comes first: out of memory leaves y untouched
+    if (x_host) SPMV_RETURN_IF(ensure_stage(p, &p->x_stage, p->n));
+    if (!y_dev) SPMV_RETURN_IF(ensure_stage(p, &p->y_stage, p->m));
+    SPMV_RETURN_IF(axpby_scratch(p, ab.beta));
+    const double *dx = x_host || staged ? p->x_stage : x;
+    double *dy = y_dev ? y : p->y_stage;
+    // opt_cusparse.cpp:72 -- H2D copy of x on every call
+    if (x_host && p->n) SPMV_HIP_TRY(hipMemcpyAsync(p->x_stage, x, sizeof(double) * p->n, hipMemcpyHostToDevice, p->stream));
+    // beta != 0: y is an input: a host y travels up, then down
+    if (ab.beta != 0.0 && !y_dev && p->m)
+        SPMV_HIP_TRY(hipMemcpyAsync(p->y_stage, y, sizeof(double) * p->m, hipMemcpyHostToDevice, p->stream));
+    SPMV_RETURN_IF(axpby_dispatch(p, ab, dx, dy));
+    const bool y_host = !y_dev && !y_staged;
+    p->y_staged = y_staged;
+    // opt_cusparse.cpp:82 -- D2H copy of y on every call
+    if (y_host && p->m) SPMV_HIP_TRY(hipMemcpyAsync(y, dy, sizeof(double) * p->m, hipMemcpyDeviceToHost, p->stream));
+    return finish_execute(p, flags, y_host);
+}
+
+// Capture `reps` dispatches on a private stream (the plan's stream may be the
+// null stream, which cannot be captured); the plan's stream is restored
+// whatever happens.
+static int graph_capture(spmv_plan_s *p, const double *x, double *y, int32_t reps, hipGraph_t *out) {
+    hipStream_t cs = nullptr;
+    SPMV_HIP_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+    const hipStream_t saved = p->stream;
+    const int saved_prof = p->prof_k;
+    p->stream = cs;
+    p->prof_k = -1;  // no profile events inside the graph
+    int st = SPMV_SUCCESS;
+    hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+    if (e == hipSuccess) {
+        for (int32_t r = 0; r < reps && st == SPMV_SUCCESS; ++r) st = dispatch(p, x, y);
+        hipGraph_t g = nullptr;
+        const hipError_t e2 = hipStreamEndCapture(cs, &g);
+        if (st == SPMV_SUCCESS && e2 != hipSuccess) e = e2;
+        if (st == SPMV_SUCCESS && e == hipSuccess) *out = g;
+        else if (g) (void)hipGraphDestroy(g);
+    }
+    p->stream = saved;
+    p->prof_k = saved_prof;
+    (void)hipStreamDestroy(cs);
+    if (st != SPMV_SUCCESS) return st;
+    if (e != hipSuccess) {
+        set_error(std::string("graph capture: ") + hipGetErrorString(e));
+        (void)hipGetLastError();
+        return SPMV_ERROR_HIP;
+    }
+    return SPMV_SUCCESS;
+}
+
+// ---- multi-vector execute (Y = A X, k interleaved right-hand sides) ---------
+
+// Widths with a fused kernel (k_dia.hip, k_ell.hip), per format, widest first.
+// Every width that beat K single-vector executes on the same plan is listed
+// (DESIGN §3.7); a width that is not listed is cut narrower.
+static const int kMultiWidthsDia[] = {8, 4, 2};
+static const int kMultiWidthsEll[] = {8, 4, 2};
+
+static bool multi_format_fused(const spmv_plan_s *p) {
+    // JDS: overflow rows take the generic path, as HYB does
+    return p->format == SPMV_FORMAT_DIA || p->format == SPMV_FORMAT_ELL || jds_without_overflow(p);
+}
+
+static bool multi_width_listed(const spmv_plan_s *p, int w) {
+    const int *tab = p->format == SPMV_FORMAT_DIA ? kMultiWidthsDia : kMultiWidthsEll;
+    for (int i = 0; i < 3; ++i)
+        if (tab[i] == w) return true;
+    return false;
+}
+
+// The cut of k columns: greedily 8, 4, 2 (the listed widths), then single
+// columns -- block starts are even.  A block is fused when the format has a
+// kernel, its X and Y block addresses are 16-byte aligned and ldx, ldy are
+// even; else each of its columns is a width-1 block of the generic path.
+static void multi_cut(const spmv_plan_s *p, int32_t k, uintptr_t x_addr, int64_t ldx, uintptr_t y_addr, int64_t ldy,
+                      std::vector<int32_t> &widths) {
+    widths.clear();
+    const bool fmt = multi_format_fused(p);
+    const bool even = ldx % 2 == 0 && ldy % 2 == 0;
+    int32_t j = 0;
+    while (j < k) {
+        int w = 1;
+        for (int c : {8, 4, 2})
+            if (k - j >= c && (!fmt || multi_width_listed(p, c))) {
+                w = c;
+                break;
+            }
+        const bool fused = w >= 2 && fmt && even && ((x_addr + sizeof(double) * (size_t)j) & 15) == 0 &&
+                           ((y_addr + sizeof(double) * (size_t)j) & 15) == 0;
+        if (fused) widths.push_back(w);
+        else widths.insert(widths.end(), (size_t)w, 1);
+        j += w;
+    }
+}
+
+static int multi_check_args(int32_t k, const double *X, int64_t ldx, const double *Y, int64_t ldy, uint32_t flags) {
+    (void)X;
+    (void)Y;
+    SPMV_CHECK_ARG(!(flags & (SPMV_X_STAGED | SPMV_Y_STAGED)),
+                   "multi execute: SPMV_X_STAGED / SPMV_Y_STAGED are not supported");
+    SPMV_CHECK_ARG(k >= 1 && k <= SPMV_MULTI_MAX, "multi execute: k outside [1, SPMV_MULTI_MAX]");
+    SPMV_CHECK_ARG(ldx >= k, "multi execute: ldx < k");
+    SPMV_CHECK_ARG(ldy >= k, "multi execute: ldy < k");
+    return SPMV_SUCCESS;
+}
+
+// the column scratch of the generic path: n + m doubles of plain hipMalloc
+// memory (COO adds into it with f64 atomics), allocated at the first use
+static int multi_scratch(spmv_plan_s *p) {
+    if (p->m_scratch) return SPMV_SUCCESS;
+    void *q = nullptr;
+    SPMV_RETURN_IF(p->arena.alloc_plain(&q, sizeof(double) * (size_t)std::max<int64_t>(p->n + p->m, 1)));
+    p->m_scratch = (double *)q;
+    return SPMV_SUCCESS;
+}
+
+// the launches of one multi execute on device blocks, on p->stream
+static int multi_dispatch(spmv_plan_s *p, int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy) {
+    if (p->m == 0) return SPMV_SUCCESS;
+    std::vector<int32_t> widths;
+    multi_cut(p, k, reinterpret_cast<uintptr_t>(X), ldx, reinterpret_cast<uintptr_t>(Y), ldy, widths);
+    int32_t j = 0;
+    for (const int32_t w : widths) {
+        if (w >= 2) {
+            if (p->format == SPMV_FORMAT_DIA) SPMV_RETURN_IF(launch_dia_multi(p, w, X + j, ldx, Y + j, ldy));
+            else SPMV_RETURN_IF(launch_ell_multi(p, w, X + j, ldx, Y + j, ldy));
+        } else {
+            // a contiguous column (ld = 1, hence k = 1) is read / written in place
+            const double *xs = X;
+            double *ys = Y;
+            if (ldx != 1 || ldy != 1) SPMV_RETURN_IF(multi_scratch(p));
+            if (ldx != 1) {
+                SPMV_RETURN_IF(launch_multi_copy(p, p->n, X + j, ldx, p->m_scratch, 1));
+                xs = p->m_scratch;
+            }
+            if (ldy != 1) ys = p->m_scratch + p->n;
+            SPMV_RETURN_IF(dispatch(p, xs, ys));
+            if (ldy != 1) SPMV_RETURN_IF(launch_multi_copy(p, p->m, ys, 1, Y + j, ldy));
+        }
+        j += w;
+    }
+    return SPMV_SUCCESS;
+}
+
+// a host staging block of at least `need` doubles
+static int multi_stage(spmv_plan_s *p, double **buf, int64_t *cap, int64_t need) {
+    if (*buf && *cap >= need) return SPMV_SUCCESS;
+    if (*buf) p->arena.free(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    SPMV_RETURN_IF(plan_alloc(p, buf, need));
+    *cap = need;
+    return SPMV_SUCCESS;
+}
+
+}  // namespace spmv
+
+using namespace spmv;
+
+extern "C" {
+
+struct spmv_graph_s {
+    spmv_plan_t plan = nullptr;  // launches use the plan's stream; destroy does not touch it
+    int device = 0;              // the plan's device, for destroy
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    int32_t reps = 0;
+};
+
+int spmv_set_stream(spmv_plan_t p, void *stream) {
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    p->stream = (hipStream_t)stream;
+    return SPMV_SUCCESS;
+}
+
+int spmv_execute(spmv_plan_t p, const double *x, double *y, uint32_t flags) {
+    return execute_impl(p, Axpby{1.0, 0.0}, x, y, flags, false);
+}
+
+int spmv_execute_alpha(spmv_plan_t p, double alpha, const double *x, double *y, uint32_t flags) {
+    return execute_impl(p, Axpby{alpha, 0.0}, x, y, flags, false);
+}
+
+int spmv_execute_axpby(spmv_plan_t p, double alpha, const double *x, double beta, double *y, uint32_t flags) {
+    return execute_impl(p, Axpby{alpha, beta}, x, y, flags, true);
+}
+
+int spmv_fetch_y(spmv_plan_t p, double *y) {
+    SPMV_CHECK_ARG(p != nullptr && (y != nullptr || p->m == 0), "plan or y is NULL");
+    SPMV_CHECK_ARG(p->y_staged && p->y_stage, "spmv_fetch_y without a previous SPMV_Y_STAGED execute");
+    SPMV_RETURN_IF(bind_device(p));
+    if (p->m) SPMV_HIP_TRY(hipMemcpyAsync(y, p->y_stage, sizeof(double) * p->m, hipMemcpyDeviceToHost, p->stream));
+    SPMV_HIP_TRY(hipStreamSynchronize(p->stream));
+    return SPMV_SUCCESS;
+}
+
+int spmv_time(spmv_plan_t p, const double *x_dev, double *y_dev, int32_t iters, double *ms) {
+    SPMV_CHECK_ARG(p != nullptr && ms != nullptr && iters > 0, "bad arguments");
+    SPMV_RETURN_IF(bind_device(p));
+    return time_on_stream(p->stream, iters, ms, [&] { return dispatch(p, x_dev, y_dev); });
+}
+
+int spmv_time_axpby(spmv_plan_t p, double alpha, const double *x_dev, double beta, double *y_dev, int32_t iters,
+                    double *ms) {
+    SPMV_CHECK_ARG(p != nullptr && ms != nullptr && iters > 0, "bad arguments");
+    SPMV_CHECK_ARG((x_dev != nullptr || p->n == 0) && (y_dev != nullptr || p->m == 0), "x or y is NULL");
+    SPMV_RETURN_IF(bind_device(p));
+    p->y_staged = false;
+    SPMV_RETURN_IF(axpby_scratch(p, beta));
+    const Axpby ab{alpha, beta};
+    return time_on_stream(p->stream, iters, ms, [&] { return axpby_dispatch(p, ab, x_dev, y_dev); });
+}
+
+int spmv_axpby_path(spmv_plan_t p, int32_t *fused) {
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    SPMV_CHECK_ARG(fused != nullptr, "fused out-pointer is NULL");
+    *fused = axpby_fused(p) ? 1 : 0;
+    return SPMV_SUCCESS;
+}
+
+int spmv_execute_multi(spmv_plan_t p, int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy,
+                       uint32_t flags) {
+    SPMV_RETURN_IF(multi_check_args(k, X, ldx, Y, ldy, flags));
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    SPMV_CHECK_ARG((X != nullptr || p->n == 0) && (Y != nullptr || p->m == 0), "multi execute: X or Y is NULL");
+    SPMV_RETURN_IF(bind_device(p));
+    p->y_staged = false;  // like any other non-staged execute (spmv_fetch_y)
+    const int64_t kp = (k + 1) & ~1;  // staging pitch: host callers always qualify for the fused path
+    const bool y_host = !(flags & SPMV_Y_DEVICE);
+    const double *dX = X;
+    double *dY = Y;
+    int64_t dldx = ldx, dldy = ldy;
+    if (!(flags & SPMV_X_DEVICE)) {
+        SPMV_RETURN_IF(multi_stage(p, &p->mx_stage, &p->mx_cap, p->n * kp));
+        if (p->n)
+            SPMV_HIP_TRY(hipMemcpy2DAsync(p->mx_stage, sizeof(double) * kp, X, sizeof(double) * ldx,
+                                          sizeof(double) * k, (size_t)p->n, hipMemcpyHostToDevice, p->stream));
+        dX = p->mx_stage;
+        dldx = kp;
+    }
+    if (y_host) {
+        SPMV_RETURN_IF(multi_stage(p, &p->my_stage, &p->my_cap, p->m * kp));
+        dY = p->my_stage;
+        dldy = kp;
+    }
+    SPMV_RETURN_IF(multi_dispatch(p, k, dX, dldx, dY, dldy));
+    if (y_host && p->m)
+        SPMV_HIP_TRY(hipMemcpy2DAsync(Y, sizeof(double) * ldy, dY, sizeof(double) * kp, sizeof(double) * k,
+                                      (size_t)p->m, hipMemcpyDeviceToHost, p->stream));
+    return finish_execute(p, flags, y_host);
+}
+
+int spmv_multi_path(spmv_plan_t p, int32_t k, const double *X, int64_t ldx, const double *Y, int64_t ldy,
+                    uint32_t flags, int32_t *widths, int32_t cap, int32_t *n_blocks) {
+    SPMV_RETURN_IF(multi_check_args(k, X, ldx, Y, ldy, flags));
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    SPMV_CHECK_ARG(n_blocks != nullptr && (widths != nullptr || cap <= 0), "n_blocks or widths is NULL");
+    // host blocks are staged at an aligned base with pitch k rounded up to even
+    const int64_t kp = (k + 1) & ~1;
+    const bool xd = (flags & SPMV_X_DEVICE) != 0, yd = (flags & SPMV_Y_DEVICE) != 0;
+    std::vector<int32_t> w;
+    multi_cut(p, k, xd ? reinterpret_cast<uintptr_t>(X) : 0, xd ? ldx : kp, yd ? reinterpret_cast<uintptr_t>(Y) : 0,
+              yd ? ldy : kp, w);
+    *n_blocks = (int32_t)w.size();
+    for (int32_t b = 0; b < *n_blocks && b < cap; ++b) widths[b] = w[b];
+    return SPMV_SUCCESS;
+}
+
+int spmv_time_multi(spmv_plan_t p, int32_t k, const double *X_dev, int64_t ldx, double *Y_dev, int64_t ldy,
+                    int32_t iters, double *ms) {
+    SPMV_RETURN_IF(multi_check_args(k, X_dev, ldx, Y_dev, ldy, 0));
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    SPMV_CHECK_ARG(ms != nullptr && iters > 0, "ms is NULL or iters < 1");
+    SPMV_CHECK_ARG((X_dev != nullptr || p->n == 0) && (Y_dev != nullptr || p->m == 0), "multi execute: X or Y is NULL");
+    SPMV_RETURN_IF(bind_device(p));
+    p->y_staged = false;
+    return time_on_stream(p->stream, iters, ms, [&] { return multi_dispatch(p, k, X_dev, ldx, Y_dev, ldy); });
+}
+
+int spmv_graph_create(spmv_plan_t p, const double *x_dev, double *y_dev, int32_t reps, spmv_graph_t *out) {
+    SPMV_CHECK_ARG(out != nullptr, "graph out-pointer is NULL");
+    *out = nullptr;
+    SPMV_CHECK_ARG(p != nullptr && reps > 0, "bad arguments");
+    SPMV_CHECK_ARG((x_dev != nullptr || p->n == 0) && (y_dev != nullptr || p->m == 0), "x or y is NULL");
+    if (p->format == SPMV_FORMAT_CSS) {
+        // the sweep's progress flags are tagged with a per-launch sequence
+        // number passed as a kernel argument: a replayed graph would repeat it
+        set_error("spmv_graph_create: CSS plans cannot be replayed from a graph");
+        return SPMV_ERROR_NOT_SUPPORTED;
+    }
+    SPMV_RETURN_IF(bind_device(p));
+    hipGraph_t g = nullptr;
+    SPMV_RETURN_IF(graph_capture(p, x_dev, y_dev, reps, &g));
+    hipGraphExec_t ex = nullptr;
+    const hipError_t e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+    if (e != hipSuccess) {
+        (void)hipGraphDestroy(g);
+        set_error(std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+        (void)hipGetLastError();
+        return SPMV_ERROR_HIP;
+    }
+    spmv_graph_s *G = new (std::nothrow) spmv_graph_s;
+    if (!G) {
+        (void)hipGraphExecDestroy(ex);
+        (void)hipGraphDestroy(g);
+        set_error("host allocation of the graph failed");
+        return SPMV_ERROR_OUT_OF_MEMORY;
+    }
+    G->plan = p;
+    G->device = p->device;
+    G->graph = g;
+    G->exec = ex;
+    G->reps = reps;
+    *out = G;
+    return SPMV_SUCCESS;
+}
+
+int spmv_graph_launch(spmv_graph_t G, uint32_t flags) {
+    SPMV_CHECK_ARG(G != nullptr && G->exec != nullptr, "graph is NULL");
+    SPMV_RETURN_IF(bind_device(G->plan));
+    SPMV_HIP_TRY(hipGraphLaunch(G->exec, G->plan->stream));
+    if (!(flags & SPMV_ASYNC)) SPMV_HIP_TRY(hipStreamSynchronize(G->plan->stream));
+    return SPMV_SUCCESS;
+}
+
+int spmv_graph_time(spmv_graph_t G, int32_t launches, double *ms) {
+    SPMV_CHECK_ARG(G != nullptr && G->exec != nullptr && ms != nullptr && launches > 0, "bad arguments");
+    SPMV_RETURN_IF(bind_device(G->plan));
+    const hipStream_t s = G->plan->stream;
+    return time_on_stream(s, launches, ms, [&]() -> int {
+        SPMV_HIP_TRY(hipGraphLaunch(G->exec, s));
+        return SPMV_SUCCESS;
+    });
+}
+
+int spmv_graph_destroy(spmv_graph_t G) {
+    if (!G) return SPMV_SUCCESS;
+    // the plan may already be gone (the header asks for graphs first, but a
+    // destroy must not read it): bind the recorded device only
+    (void)hipSetDevice(G->device);
+    if (G->exec) (void)hipGraphExecDestroy(G->exec);
+    if (G->graph) (void)hipGraphDestroy(G->graph);
+    delete G;
+    return SPMV_SUCCESS;
+}
+
+static const char *const kPhases[][3] = {
+    {"", "", ""},           {"csr", "", ""},   {"ell", "", ""},     {"tile", "fixup", ""},
+    {"dia", "", ""},        {"ell", "overflow", ""}, {"sweep", "", ""}, {"zero_y", "segment", ""},
+    {"ell", "overflow", ""}};
+
+const char *spmv_phase_name(spmv_plan_t p, int32_t k) {
+    static const char *const kBinPhases[8] = {"mul", "sum", "mul.1", "sum.1", "mul.2", "sum.2", "mul.3", "sum.3"};
+    if (p && p->format == SPMV_FORMAT_BIN) {
+        if (!p->bin.reuse) return k == 0 ? "mul" : k == 1 ? "sum" : "";  // groups' Mul launches: one phase
+        return k >= 0 && k < 8 && k < 2 * p->bin.G ? kBinPhases[k] : "";
+    }
+    if (!p || k < 0 || k > 2 || p->format < 0 || p->format > SPMV_FORMAT_JDS) return "";
+    return kPhases[p->format][k];
+}
+
+int spmv_profile(spmv_plan_t p, const double *x_dev, double *y_dev, int32_t iters, double *phase_ms,
+                 int32_t max_phases, int32_t *n_phases) {
+    SPMV_CHECK_ARG(p != nullptr && iters > 0 && phase_ms != nullptr && n_phases != nullptr && max_phases > 0,
+                   "bad arguments");
+    SPMV_RETURN_IF(bind_device(p));
+    for (auto &e : p->prof_ev) SPMV_HIP_TRY(hipEventCreate(&e));
+    std::vector<double> acc(8, 0.0);
+    int nph = 1, st = SPMV_SUCCESS;
+    for (int i = 0; i < iters && st == SPMV_SUCCESS; ++i) {
+        p->prof_k = 0;
+        (void)hipEventRecord(p->prof_ev[0], p->stream);
+        st = dispatch(p, x_dev, y_dev);
+        const int k = p->prof_k;
+        p->prof_k = -1;
+        (void)hipEventRecord(p->prof_ev[k + 1], p->stream);
+        if (hipEventSynchronize(p->prof_ev[k + 1]) != hipSuccess) {
+            st = SPMV_ERROR_HIP;
+            set_error("spmv_profile: event synchronisation failed");
+            break;
+        }
+        nph = k + 1;
+        for (int j = 0; j <= k; ++j) {
+            float f = 0;
+            (void)hipEventElapsedTime(&f, p->prof_ev[j], p->prof_ev[j + 1]);
+            acc[j] += f;
+        }
+    }
+    p->prof_k = -1;
+    for (auto &e : p->prof_ev) (void)hipEventDestroy(e);
+    *n_phases = nph;
+    for (int j = 0; j < std::min(nph, max_phases); ++j) phase_ms[j] = acc[j] / iters;
+    return st;
+}
+
+}  // extern "C"

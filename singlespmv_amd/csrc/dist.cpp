@@ -204,9 +204,7 @@ int spmv_dist_create_csr(int32_t n_devices, const int32_t *devices, int64_t m, i
     }
     d->cuts.assign((size_t)n_devices + 1, 0);
     int st = spmv_dist_layout(row_ptr, m, n_devices, d->cuts.data(), &d->slice);
-    spmv_options_t o;
-    if (opt) o = *opt;
-    else spmv_options_default(&o);
+    spmv_options_t o = resolve_options(opt);
     std::vector<int64_t> rp;
     for (int k = 0; k < n_devices && st == SPMV_SUCCESS; ++k) {
         const int dev = d->devs[k];

@@ -34,6 +34,14 @@ int DevArena::alloc(void **p, size_t n) {
     return SPMV_SUCCESS;
 }
 
+int DevArena::alloc_plain(void **p, size_t n) {
+    const size_t keep = vmm_min;
+    vmm_min = 0;
+    const int st = alloc(p, n);
+    vmm_min = keep;
+    return st;
+}
+
 // Physical memory in `chunk`-byte handles (hipMemCreate) mapped back to back
 // into one reserved VA range.  chunk is rounded to the allocation granularity.
 int DevArena::alloc_vmm(void **p, size_t n, size_t chunk, int device, size_t align) {

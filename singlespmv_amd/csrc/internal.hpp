@@ -1,5 +1,5 @@
 // internal.hpp -- plan layout, error plumbing and launcher declarations shared
-// by the C-ABI (capi.cpp), the host format builders (formats.cpp) and the
+// by the C-ABI (capi*.cpp), the host format builders (formats.cpp) and the
 // kernels (k_*.hip).  Not installed; the public surface is include/spmv_hip.h.
 #pragma once
 
@@ -44,10 +44,13 @@ const char *last_error();
         if (s_ != SPMV_SUCCESS) return s_;                                      \
     } while (0)
 
+// a helper shared by the files of the C-ABI: not a dynamic symbol of the library
+#define SPMV_LOCAL __attribute__((visibility("hidden")))
+
 // Transient device scratch of the plan builders (freed before create
 // returns): a failed allocation clears HIP's sticky error (a later launch
 // check must not see it) and reports SPMV_ERROR_OUT_OF_MEMORY, so the
-// host-CSR routing falls back to the host builders (capi.cpp) instead of
+// host-CSR routing falls back to the host builders (capi_create.cpp) instead of
 // failing a plan the host path builds fine.
 inline int scratch_malloc_bytes(void **q, size_t n, const char *what) {
     *q = nullptr;
@@ -121,6 +124,9 @@ struct DevArena {
     int device = 0;
     size_t vmm_min = 0;  // > 0: alloc() of >= vmm_min bytes maps 2-MB VMM handles instead
     int alloc(void **p, size_t n);  // hipMalloc (or VMM, above), zero-size safe
+    // always hipMalloc, whatever vmm_min says: what a plan allocates after its
+    // build (execute scratch, refresh maps and staging; no 2-MB rounding)
+    SPMV_LOCAL int alloc_plain(void **p, size_t n);
     // n bytes of physical memory in `chunk`-byte handles mapped at one VA range
     // (align > 0: the mapping starts at a multiple of `align` inside a larger
     // reservation -- hipMemAddressReserve itself honours only the granularity)
@@ -692,5 +698,26 @@ bool is_value_array(const char *name);
 int launch_iota_values(hipStream_t st, double *val, int64_t nnz);  // val[i] = i + 1
 int update_prepare_from_shadow(spmv_plan_s *p, const spmv_plan_s *shadow);
 int launch_update_values(const spmv_plan_s *p, const double *d_val);
+
+// ---- what the files of the C-ABI share ------------------------------------
+// capi_create.cpp.  resolve_options: *opt, or the defaults for a null opt.
+SPMV_LOCAL spmv_options_t resolve_options(const spmv_options_t *opt);
+// every pointer device memory on `dev`?  (else INVALID_VALUE, error = who + what)
+SPMV_LOCAL int check_device_arrays(const void *const *ptrs, int count, int dev, const char *who,
+                                   const char *what = ": arrays must be device memory on the plan's device");
+// The plan of a CSR in HBM, built on the device and nowhere else (A.h_rp is
+// not read; opts->device as spmv_options_t::device).  Checks everything a
+// caller's CSR needs (spmv_plan_create_csr_device's texts).  A plan the device
+// builders do not make (BIN rows out of strip order when the device has no
+// room for their sorted copy) comes back as kNeedHostBuild with *opts resolved
+// for the host builders: format chosen, crs_exact's rewrites applied, build =
+// HOST, device = the one bound.  A caller that holds the host CSR hands it to
+// them; one that does not takes create_staged_on_host: the CSR copied to host
+// memory, then the host builders on it.
+constexpr int kNeedHostBuild = -2000;
+SPMV_LOCAL int create_on_device(const DevCsr &A, spmv_options_t *opts, spmv_plan_t *out);
+SPMV_LOCAL int create_staged_on_host(const DevCsr &A, const spmv_options_t &o, spmv_plan_t *out);
+// capi_execute.cpp: make the plan's device the current one
+SPMV_LOCAL int bind_device(const spmv_plan_s *p);
 
 }  // namespace spmv

@@ -1,6 +1,6 @@
 // k_axpby.hip -- the second pass of spmv_execute_axpby's generic path:
 // y = alpha * t + beta * y over m rows, t = the row sums the plan's own
-// kernels wrote into the plan's scratch (capi.cpp axpby_dispatch).  The fused
+// kernels wrote into the plan's scratch (capi_execute.cpp axpby_dispatch).  The fused
 // path -- the same arithmetic in the store epilogue of the one-writer-per-row
 // kernels -- lives in k_csr.hip, k_ell.hip and k_dia.hip.
 #include "build_util.hpp"

@@ -179,7 +179,7 @@ __global__ void csr_val_halves_kernel(const double *__restrict__ val, int64_t nn
     }
 }
 
-// input checks of validate_csr (capi.cpp) on device data: bad[0] counts
+// input checks of validate_csr (capi_create.cpp) on device data: bad[0] counts
 // decreasing row pointers, bad[1] columns outside [0, n)
 __global__ void check_csr(const int64_t *__restrict__ rp, int64_t m, const int32_t *__restrict__ col, int64_t nnz,
                           int64_t n, unsigned long long *__restrict__ bad) {

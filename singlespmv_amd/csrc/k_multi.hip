@@ -4,7 +4,7 @@
 // the zero fill of a plan with nothing stored.
 //
 // The fused kernels (DIA, sliced ELL / JDS; K = 2, 4, 8) are the K-templated
-// bodies of k_dia.hip and k_ell.hip.  capi.cpp's multi_cut decides which
+// bodies of k_dia.hip and k_ell.hip.  capi_execute.cpp's multi_cut decides which
 // columns take which path.
 #include "build_util.hpp"
 #include "device.hpp"

@@ -2,7 +2,7 @@
 // (spmv_csr_transpose_device; the plans of the transpose are built from its
 // output).  Output row c holds A's entries of column c in ascending source
 // entry index: a stable sort of the entries by column, byte for byte what
-// transpose_csr_host (capi.cpp) gives.
+// transpose_csr_host (capi_create.cpp) gives.
 //
 //   1. keys = columns, ids = 0 .. nnz-1, stably radix-sorted (sort_pairs_u32:
 //      the BIN builder's hipCUB instance, the significant bits of n - 1 only;

@@ -241,8 +241,6 @@ int update_prepare_from_shadow(spmv_plan_s *p, const spmv_plan_s *shadow) {
     UpdState u;
     u.wide = p->nnz >= (int64_t)INT32_MAX;
     u.dia_add = p->format == SPMV_FORMAT_DIA;
-    const size_t keep = p->arena.vmm_min;
-    p->arena.vmm_min = 0;
     int st = SPMV_SUCCESS;
     for (size_t k = 0; k < pa.size() && st == SPMV_SUCCESS; ++k) {
         if (!is_value_array(pa[k].name)) continue;
@@ -254,10 +252,9 @@ int update_prepare_from_shadow(spmv_plan_s *p, const spmv_plan_s *shadow) {
         UpdArray a;
         a.dst = (double *)const_cast<void *>(pa[k].ptr);
         a.slots = pa[k].bytes / 8;
-        st = p->arena.alloc(&a.map, (size_t)a.slots * (u.wide ? 8 : 4));
+        st = p->arena.alloc_plain(&a.map, (size_t)a.slots * (u.wide ? 8 : 4));
         if (st == SPMV_SUCCESS) u.arrays.push_back(a);
     }
-    p->arena.vmm_min = keep;
     auto drop = [&]() {
         (void)hipStreamSynchronize(p->stream);
         for (const UpdArray &a : u.arrays) p->arena.free(a.map);
