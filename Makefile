@@ -5,9 +5,10 @@
 #                      oracle/liboracle.so             (test oracle, CPU)
 #   make ref        -> oracle/_ref/*.so from /root/reference/src (if present)
 #   make probes     -> probes_build/libspmv_hip.so: the same library with the
-#                      experiment switches (SPMV_<FMT>_* env variables,
-#                      ablation kernels) compiled in, for tools/ only; load it
-#                      with SPMV_HIP_LIBRARY=probes_build/libspmv_hip.so
+#                      experiment switches of DESIGN.md §9.1 (environment
+#                      variables read through probe_env) compiled in, for
+#                      tools/ only; load it with
+#                      SPMV_HIP_LIBRARY=probes_build/libspmv_hip.so
 #
 # Everything is built in-tree so the .so files travel to the GPU box with the
 # snapshot (they are git-ignored, not gpurun-ignored).

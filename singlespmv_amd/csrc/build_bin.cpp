@@ -34,13 +34,6 @@ static int bin_params(spmv_plan_s *p, const spmv_options_t &o, int64_t m, int64_
     const int64_t C = B.strip;
     B.nwg1 = ncu;  // one 1024-thread workgroup per CU (the x strip fills the LDS)
     B.nwg2 = ncu;  // 160 KB of LDS y slices per workgroup
-    if (const char *e = probe_env("SPMV_BIN_CUS")) {  // experiment: a subset of the CUs
-        const int k = std::atoi(e);
-        if (k > 0 && k < ncu) {
-            B.nwg1 = k;
-            B.nwg2 = k;
-        }
-    }
     // internal tuning knobs; defaults measured at config 2
     // (profiles/round1/probe/bin_probe_c2.jsonl): 16-entry (128-B) product
     // lines and 4 Sum waves (5119-row bins, ~1 KB segments) took Mul from
@@ -89,11 +82,6 @@ static int bin_params(spmv_plan_s *p, const spmv_options_t &o, int64_t m, int64_
         SPMV_CHECK_ARG(o.bin_pad == 8 || o.bin_pad == 16 || o.bin_pad == 32, "bin_pad must be 0, 8, 16 or 32");
         B.pad_log = o.bin_pad == 8 ? 3 : o.bin_pad == 16 ? 4 : 5;
     }
-    if (const char *e = probe_env("SPMV_BIN_PADLOG")) B.pad_log = std::min(5, std::max(3, std::atoi(e)));
-    if (const char *e = probe_env("SPMV_BIN_SUMWAVES")) {
-        const int w = std::atoi(e);
-        B.sum_waves = w == 2 || w == 4 ? w : 8;
-    }
     // probe build: one product buffer re-used per row group (read here, before
     // bin_mo_resolve, which needs it)
     if (const char *e = probe_env("SPMV_BIN_REUSE")) B.reuse = std::atoi(e) != 0;
@@ -103,7 +91,6 @@ static int bin_params(spmv_plan_s *p, const spmv_options_t &o, int64_t m, int64_
     SPMV_CHECK_ARG(o.bin_product_order >= SPMV_BIN_ORDER_AUTO && o.bin_product_order <= SPMV_BIN_ORDER_MUL,
                    "bin_product_order must be 0, 1 or 2");
     B.order_req = o.bin_product_order;
-    if (const char *e = probe_env("SPMV_BIN_ORDER")) B.order_req = std::atoi(e);
     B.max_rows = bin_max_rows(B.sum_waves);
     B.sum_u = B.sum_waves == 8 ? 8 : 32;  // must match launch_sum's <W2, U> pairs
     p->algo_bytes = 12 * nnz + 8 * n + 8 * m;
@@ -216,7 +203,7 @@ static void bin_mo_resolve(BinDev &B, const spmv_options_t &o, int64_t LL, int64
     const bool want = B.order_req == SPMV_BIN_ORDER_MUL ||
                       (B.order_req == SPMV_BIN_ORDER_AUTO && B.seg_est < kBinMulOrderMaxSeg);
     B.mo = want && LL == 0 && o.bin_groups <= 1 && !B.reuse && B.sum_u == 32 && nnz + kBinProdSlack < ((int64_t)1 << 31);
-    if (B.mo && !o.bin_pad && !probe_env("SPMV_BIN_PADLOG")) B.pad_log = 3;
+    if (B.mo && !o.bin_pad) B.pad_log = 3;
 }
 
 // ---- row bins: <= max_rows rows, cut at cumulative nnz targets; a multiple
@@ -606,8 +593,6 @@ static int alloc_prod_plain(spmv_plan_s *p, size_t prod_bytes) {
 static int bin_place_search(spmv_plan_s *p, int64_t n, size_t prod_bytes) {
     BinDev &B = p->bin;
     int K = 8;
-    if (const char *e = probe_env("SPMV_BIN_PLACEMENT")) K = std::max(1, std::min(12, std::atoi(e)));
-    if (K == 1) return alloc_prod_plain(p, prod_bytes);
     double *xz = nullptr;
     SPMV_RETURN_IF(scratch_malloc(&xz, sizeof(double) * (size_t)std::max<int64_t>(n, 1), "xz"));
     if (const hipError_t e = hipMemset(xz, 0, sizeof(double) * (size_t)std::max<int64_t>(n, 1)); e != hipSuccess) {
@@ -625,8 +610,6 @@ static int bin_place_search(spmv_plan_s *p, int64_t n, size_t prod_bytes) {
     // spaced ones fast, profiles/round1/probe/bin_placement_spacers.jsonl).
     // Spacers only when the device has room for them with 8 GB to spare.
     int64_t gap_mb = 16384;
-    const char *gap_env = probe_env("SPMV_BIN_PLACEMENT_GAP_MB");
-    if (gap_env) gap_mb = std::atoll(gap_env);
     {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
@@ -637,10 +620,8 @@ static int bin_place_search(spmv_plan_s *p, int64_t n, size_t prod_bytes) {
         // 16 GB): memory freed by an earlier plan's search tends to be
         // the slow kind, and equal 16 GB steps left every candidate of
         // a second plan inside it (bin_placement_k8_default.txt)
-        if (!gap_env) {
-            const size_t rest = (size_t)K * prod_bytes + ((size_t)8 << 30);
-            if (free_b > rest) gap_mb = std::max<int64_t>(gap_mb, (int64_t)((free_b - rest) / (size_t)(K - 1) >> 20));
-        }
+        const size_t rest = (size_t)K * prod_bytes + ((size_t)8 << 30);
+        if (free_b > rest) gap_mb = std::max<int64_t>(gap_mb, (int64_t)((free_b - rest) / (size_t)(K - 1) >> 20));
         // as many spaced candidates as fit (at least 2), else 4 unspaced
         auto need = [&](int k) {
             return (size_t)(k - 1) * ((size_t)gap_mb << 20) + (size_t)k * prod_bytes + ((size_t)8 << 30);
@@ -695,7 +676,6 @@ static int bin_place_prod(spmv_plan_s *p, int64_t n, size_t prod_bytes, const sp
     BinDev &B = p->bin;
     int mode = o.placement;
     SPMV_RETURN_IF(placement_mode_check(mode));
-    if (const char *e = probe_env("SPMV_PLACEMENT_MODE")) mode = std::atoi(e);
     // AUTO: a product buffer of >= 32 MB is built from 2-MB physical handles
     // (hipMemCreate) mapped into one VA range aligned to 1 GB; smaller ones
     // are one plain allocation.  With one plain hipMalloc the Mul ran in a
@@ -712,11 +692,11 @@ static int bin_place_prod(spmv_plan_s *p, int64_t n, size_t prod_bytes, const sp
     B.placement = mode;
     if (mode == SPMV_PLACEMENT_SEARCH) return bin_place_search(p, n, prod_bytes);
     if (mode == SPMV_PLACEMENT_VMM) {
-        size_t chunk = kVmmChunk, align = kVmmAlign;
+        // probe build: the handle size (tools/placement_probe.py vmm:<MB>)
+        size_t chunk = kVmmChunk;
         if (const char *e = probe_env("SPMV_VMM_CHUNK_MB")) chunk = (size_t)std::max(1, std::atoi(e)) << 20;
-        if (const char *e = probe_env("SPMV_VMM_ALIGN_MB")) align = (size_t)std::max(0, std::atoi(e)) << 20;
         void *q = nullptr;
-        SPMV_RETURN_IF(p->arena.alloc_vmm(&q, prod_bytes, chunk, p->device, align));
+        SPMV_RETURN_IF(p->arena.alloc_vmm(&q, prod_bytes, chunk, p->device, kVmmAlign));
         B.prod = (double *)q;
         return SPMV_SUCCESS;
     }

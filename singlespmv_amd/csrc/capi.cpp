@@ -126,8 +126,8 @@ int spmv_plan_update_values(spmv_plan_t p, const double *val, uint32_t flags) {
     return SPMV_SUCCESS;
 }
 
-// internal (not in the public header): the CSS per-wave timestamps of the
-// last launch when the plan was built with SPMV_CSS_DEBUG & 32
+// internal (not in the public header; probe build): the CSS per-wave
+// timestamps of the last launch when the plan was built with SPMV_CSS_DEBUG & 32
 int64_t spmv_css_timestamps(spmv_plan_t p, uint64_t *out, int64_t cap) {
     if (!p || p->format != SPMV_FORMAT_CSS || !p->css.tstamp) return -1;
     const int64_t n = (int64_t)p->css.P * p->css.nwg * (kCssWorkers + 2);
@@ -135,29 +135,7 @@ int64_t spmv_css_timestamps(spmv_plan_t p, uint64_t *out, int64_t cap) {
     return n;
 }
 
-// internal: the CSS block/list layout (bstart [P*nwg+1], woff [P*nwg*15+1])
-int spmv_css_layout(spmv_plan_t p, int64_t *bstart, int64_t *woff) {
-    if (!p || p->format != SPMV_FORMAT_CSS) return -1;
-    const int64_t nb = (int64_t)p->css.P * p->css.nwg;
-    if (hipMemcpy(bstart, p->css.bstart, 8 * (size_t)(nb + 1), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    if (hipMemcpy(woff, p->css.woff, 8 * (size_t)(nb * kCssWorkers + 1), hipMemcpyDeviceToHost) != hipSuccess)
-        return -1;
-    return 0;
-}
-
-// internal (experiment): give the BIN product buffer a fresh allocation (the
-// old one is kept until the plan is destroyed, so the new one lands elsewhere)
-int spmv_bin_realloc_prod(spmv_plan_t p) {
-    if (!p || p->format != SPMV_FORMAT_BIN || !p->bin.prod) return -1;
-    void *q = nullptr;
-    if (p->arena.alloc(&q, sizeof(double) * (size_t)(std::max<int64_t>(p->bin.prod_cap, 1) + kBinProdSlack)) !=
-        SPMV_SUCCESS)
-        return -1;
-    p->bin.prod = (double *)q;
-    return 0;
-}
-
-// internal (placement experiments): the BIN product buffer
+// internal (not in the public header; tools/placement_probe.py): the BIN product buffer
 int spmv_bin_prod(spmv_plan_t p, void **buf, int64_t *bytes) {
     if (!p || p->format != SPMV_FORMAT_BIN || !p->bin.prod || !buf || !bytes) return -1;
     *buf = p->bin.prod;

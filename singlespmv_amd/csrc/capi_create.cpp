@@ -32,7 +32,6 @@ static void stream_placement(spmv_plan_s *p, int fmt, const spmv_options_t &o) {
     if (fmt == SPMV_FORMAT_BIN || fmt == SPMV_FORMAT_DIA) return;
     if (o.placement == SPMV_PLACEMENT_AUTO) p->arena.vmm_min = kStreamVmmMinBytes;
     else if (o.placement == SPMV_PLACEMENT_VMM) p->arena.vmm_min = kBinVmmMinBytes;
-    if (const char *e = probe_env("SPMV_ARENA_VMM_MB")) p->arena.vmm_min = (size_t)std::max(0, std::atoi(e)) << 20;
 }
 
 // The prologue of every create path: resolve the plan's device (requested <
@@ -69,7 +68,6 @@ static spmv_plan_s *new_plan(int dev, int64_t m, int64_t n, int64_t nnz) {
     }
     p->device = dev;
     p->arena.device = dev;
-    if (const char *e = probe_env("SPMV_ARENA_VMM_MB")) p->arena.vmm_min = (size_t)std::max(0, std::atoi(e)) << 20;
     p->m = m;
     p->n = n;
     p->nnz = nnz;

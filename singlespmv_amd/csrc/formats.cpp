@@ -74,44 +74,22 @@ int DevArena::alloc_vmm(void **p, size_t n, size_t chunk, int device, size_t ali
     hipError_t e = hipMemAddressReserve(&m.res, m.res_bytes, gran, nullptr, 0);
     if (e != hipSuccess) return undo(e, "hipMemAddressReserve");
     m.va = align ? (void *)(((uintptr_t)m.res + align - 1) / align * align) : m.res;
-    // all handles first, then mapped -- in creation order, or (probe build,
-    // SPMV_VMM_SHUFFLE) handle k at chunk slot k * P mod count
+    // all handles first, then mapped in creation order: handles[k] backs chunk k
     const size_t cnt = total / chunk;
-    // probe build, SPMV_VMM_STRIDE=K: create K times the handles and keep
-    // every K-th (the others are released once the kept ones are mapped), so
-    // physically consecutive blocks do not back consecutive chunks
-    size_t K = 1;
-    if (const char *st = probe_env("SPMV_VMM_STRIDE")) K = (size_t)std::max(1, std::min(8, std::atoi(st)));
-    std::vector<hipMemGenericAllocationHandle_t> spare;
-    for (size_t k = 0; k < cnt * K; ++k) {
+    for (size_t k = 0; k < cnt; ++k) {
         hipMemGenericAllocationHandle_t h;
         e = hipMemCreate(&h, chunk, &prop, 0);
-        if (e != hipSuccess) {
-            for (auto hs : spare) (void)hipMemRelease(hs);
-            return undo(e, "hipMemCreate");
-        }
-        if (k % K == 0) m.handles.push_back(h);
-        else spare.push_back(h);
+        if (e != hipSuccess) return undo(e, "hipMemCreate");
+        m.handles.push_back(h);
     }
-    size_t P = 1;
-    if (const char *sh = probe_env("SPMV_VMM_SHUFFLE"))
-        if (std::atoi(sh) && cnt > 2) {
-            P = (size_t)(0.6180339887 * (double)cnt) | 1;
-            while (std::gcd(P, cnt) != 1) P += 2;
-        }
-    std::vector<hipMemGenericAllocationHandle_t> slot(cnt);
-    for (size_t k = 0; k < cnt; ++k) slot[(k * P) % cnt] = m.handles[k];
-    m.handles = slot;  // handles[k] is mapped at chunk slot k
     for (size_t k = 0; k < cnt; ++k) {
         e = hipMemMap((char *)m.va + k * chunk, chunk, 0, m.handles[k], 0);
         if (e != hipSuccess) {
             for (size_t j = k; j < cnt; ++j) (void)hipMemRelease(m.handles[j]);
-            for (auto hs : spare) (void)hipMemRelease(hs);
             m.handles.resize(k);
             return undo(e, "hipMemMap");
         }
     }
-    for (auto hs : spare) (void)hipMemRelease(hs);
     hipMemAccessDesc acc = {};
     acc.location = prop.location;
     acc.flags = hipMemAccessFlagsProtReadWrite;
@@ -291,24 +269,20 @@ int csr_windows_finish(spmv_plan_s *p, const std::vector<int32_t> &lo, const std
     CsrDev &c = p->csr;
     const int64_t ng = (int64_t)lo.size();
     if (ng == 0 || p->n == 0 || p->nnz == 0) return SPMV_SUCCESS;  // no x to stage
-    for (int si = 0; si < 3; ++si) {
-        const int64_t S = (int64_t)1 << si;
-        int64_t span = 1;
+    constexpr int64_t S = kCsrSlabsPerWave;
+    int64_t span = 1;
 #pragma omp parallel for schedule(static) reduction(max : span)
-        for (int64_t b = 0; b < ng; b += S) {
-            int32_t l = std::numeric_limits<int32_t>::max(), h = -1;
-            for (int64_t g = b; g < std::min(ng, b + S); ++g) {
-                if (hi[(size_t)g] < 0) continue;  // no entries
-                l = std::min(l, lo[(size_t)g]);
-                h = std::max(h, hi[(size_t)g]);
-            }
-            if (h >= 0) span = std::max<int64_t>(span, (int64_t)h - l + 1);
+    for (int64_t b = 0; b < ng; b += S) {
+        int32_t l = std::numeric_limits<int32_t>::max(), h = -1;
+        for (int64_t g = b; g < std::min(ng, b + S); ++g) {
+            if (hi[(size_t)g] < 0) continue;  // no entries
+            l = std::min(l, lo[(size_t)g]);
+            h = std::max(h, hi[(size_t)g]);
         }
-        c.win_s[si] = span <= kCsrMaxWin ? (int32_t)span : 0;
+        if (h >= 0) span = std::max<int64_t>(span, (int64_t)h - l + 1);
     }
-    constexpr int sd = csr_win_index(kCsrSlabsPerWave);
-    if (!c.win_s[sd]) return SPMV_SUCCESS;
-    c.win = c.win_s[sd];
+    if (span > kCsrMaxWin) return SPMV_SUCCESS;
+    c.win = (int32_t)span;
     std::vector<int32_t> w0(lo);
     for (int64_t g = 0; g < ng; ++g)
         if (hi[(size_t)g] < 0) w0[(size_t)g] = std::numeric_limits<int32_t>::max();  // empty: no lower bound
@@ -335,9 +309,9 @@ static int csr_x_windows(spmv_plan_s *p, const HostCsr &A) {
 
 int build_csr(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o) {
     CsrDev &c = p->csr;
-    // 64-bit row pointers from 2^31 entries on; SPMV_CSR_FORCE_RP64 (internal)
+    // 64-bit row pointers from 2^31 entries on; spmv_options_t.csr_row_ptr64
     // exercises that kernel instance on small matrices in the tests
-    c.rp64 = A.nnz >= (int64_t)std::numeric_limits<int32_t>::max() - 64 || o.csr_row_ptr64 != 0 || probe_env("SPMV_CSR_FORCE_RP64");
+    c.rp64 = A.nnz >= (int64_t)std::numeric_limits<int32_t>::max() - 64 || o.csr_row_ptr64 != 0;
     if (c.rp64) {
         SPMV_RETURN_IF(plan_upload(p, (int64_t **)&c.row_ptr, A.row_ptr, A.m + 1));
     } else {
@@ -403,7 +377,6 @@ void ell_finish_info(spmv_plan_s *p, int maxw, int64_t total) {
 // order (JDS): slice row i is matrix row order[i]; nullptr = identity.
 int build_ell(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &, int cap, const int32_t *order) {
     EllDev &e = p->ell;
-    if (const char *u = probe_env("SPMV_ELL_UNROLL")) e.unroll = std::atoi(u);
     auto src = [&](int64_t r) -> int64_t { return order ? (int64_t)order[r] : r; };
     e.n_slices = (A.m + 63) / 64;
     std::vector<int64_t> off;
@@ -670,7 +643,6 @@ int build_ss(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o) {
         set_error("ss_sigma must be one of 4,8,12,16,20,24,32,48,64");
         return SPMV_ERROR_INVALID_VALUE;
     }
-    ss_probe_options(s);
     const int64_t T = 64 * (int64_t)s.sigma;
     const int W = ss_flag_words(s.sigma);
     s.n_tiles = (A.nnz + T - 1) / T;
@@ -740,15 +712,7 @@ void ss_finish_info(spmv_plan_s *p) {
     p->empty_rows = s.n_empty;
     p->algo_bytes = 12 * p->nnz + 8 * p->n + 8 * p->m;
     p->n_kernels = 2;
-    p->kernel_name = std::string(s.kernel == 0 && s.sigma <= 32 ? "ss_tile_kernel<" : "ss_stream_kernel<") +
-                     std::to_string(s.sigma) + ">+ss_fixup_kernel";
-}
-
-// probe build: SPMV_SS_KERNEL (0 = ss_tile_kernel), SPMV_SS_PF at plan build
-void ss_probe_options(SsDev &s) {
-    if (const char *e = probe_env("SPMV_SS_KERNEL")) s.kernel = std::atoi(e);
-    if (const char *e = probe_env("SPMV_SS_PF")) s.pf = std::atoi(e);
-    if (const char *e = probe_env("SPMV_SS_STAGE")) s.stage = std::atoi(e) != 0;
+    p->kernel_name = "ss_stream_kernel<" + std::to_string(s.sigma) + ">+ss_fixup_kernel";
 }
 
 // ---------------------------------------------------------------- DIA
@@ -788,25 +752,11 @@ int dia_placement(spmv_plan_s *p, int64_t m, int64_t n, size_t bytes, const spmv
     DiaDev &d = p->dia;
     int mode = o.placement;
     SPMV_RETURN_IF(placement_mode_check(mode));
-    if (const char *e = probe_env("SPMV_PLACEMENT_MODE")) mode = std::atoi(e);
     if (mode == SPMV_PLACEMENT_AUTO) mode = SPMV_PLACEMENT_PLAIN;
     if (mode == SPMV_PLACEMENT_SEARCH && bytes < ((size_t)256 << 20)) mode = SPMV_PLACEMENT_PLAIN;
     d.placement = mode;
-    if (mode == SPMV_PLACEMENT_PLAIN) return SPMV_SUCCESS;
-    if (mode == SPMV_PLACEMENT_VMM) {  // move the values into a VMM mapping
-        size_t chunk = kVmmChunk, align = kVmmAlign;
-        if (const char *e = probe_env("SPMV_VMM_CHUNK_MB")) chunk = (size_t)std::max(1, std::atoi(e)) << 20;
-        if (const char *e = probe_env("SPMV_VMM_ALIGN_MB")) align = (size_t)std::max(0, std::atoi(e)) << 20;
-        void *q = nullptr;
-        SPMV_RETURN_IF(p->arena.alloc_vmm(&q, bytes, chunk, p->device, align));
-        SPMV_HIP_TRY(hipMemcpy(q, d.val, bytes, hipMemcpyDeviceToDevice));
-        p->arena.free(d.val);
-        d.val = (double *)q;
-        return SPMV_SUCCESS;
-    }
+    if (mode != SPMV_PLACEMENT_SEARCH) return SPMV_SUCCESS;  // PLAIN (VMM values: the builders map them)
     int K = 8;
-    if (const char *e = probe_env("SPMV_DIA_PLACEMENT")) K = std::max(1, std::min(8, std::atoi(e)));
-    if (K <= 1) return SPMV_SUCCESS;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
         (void)hipGetLastError();
@@ -880,11 +830,6 @@ int dia_placement(spmv_plan_s *p, int64_t m, int64_t n, size_t bytes, const spmv
         if (k != best) p->arena.free(cand[k]);
     d.val = cand[best];
     d.placement_ms = t;
-    if (d.dbg & 16) {
-        std::fprintf(stderr, "[dia] placement ms:");
-        for (float tt : t) std::fprintf(stderr, " %.4f", tt);
-        std::fprintf(stderr, " -> %zu\n", best);
-    }
     return st;
 }
 
@@ -918,7 +863,7 @@ int build_dia(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o) {
     const int64_t slots = (int64_t)d.n_diags * d.mp;
     std::vector<double> val((size_t)std::max<int64_t>(slots, 1), 0.0);
     const int64_t nd = d.n_diags;
-    if (const char *e = probe_env("SPMV_DIA_GROUP")) d.group = std::max(0, std::atoi(e));
+    d.group = dia_probe_group();
     const int64_t G = d.group, nblk = d.mp / kDiaBlockRows;
 #pragma omp parallel for schedule(static)
     for (int64_t r = 0; r < A.m; ++r)
@@ -933,8 +878,6 @@ int build_dia(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o) {
             val[(size_t)at] += A.val[j];  // duplicates are summed
         }
     SPMV_RETURN_IF(plan_upload(p, &d.off, offs.data(), d.n_diags));
-    if (const char *e = probe_env("SPMV_DIA_DEBUG")) d.dbg = std::atoi(e);
-    if (const char *e = probe_env("SPMV_DIA_LDS_KB")) d.lds_kb = std::atoi(e);
     p->stored_slots = slots;
     // AUTO: values of >= 256 MB go straight into 2-MB VMM handles mapped at a
     // 1-GB-aligned VA (config 4: 1.537-1.61 ms against 1.665-1.677 with one
@@ -945,7 +888,7 @@ int build_dia(spmv_plan_s *p, const HostCsr &A, const spmv_options_t &o) {
     SPMV_RETURN_IF(placement_mode_check(oo.placement));
     if (oo.placement == SPMV_PLACEMENT_AUTO)
         oo.placement = vbytes >= kDiaVmmMinBytes ? SPMV_PLACEMENT_VMM : SPMV_PLACEMENT_PLAIN;
-    if (oo.placement == SPMV_PLACEMENT_VMM && !probe_env("SPMV_PLACEMENT_MODE")) {
+    if (oo.placement == SPMV_PLACEMENT_VMM) {
         void *q = nullptr;
         SPMV_RETURN_IF(p->arena.alloc_vmm(&q, vbytes, kVmmChunk, p->device, kVmmAlign));
         SPMV_HIP_TRY(hipMemcpy(q, val.data(), vbytes, hipMemcpyHostToDevice));
@@ -996,10 +939,6 @@ int css_layout(spmv_plan_s *p, const int64_t *row_ptr, int64_t m, int64_t n, int
     int ncu = 0;
     SPMV_HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->device));
     c.nwg = ncu > 0 ? ncu : 256;
-    if (const char *e = probe_env("SPMV_CSS_WGS")) {  // experiment: a subset of the CUs
-        const int k = std::atoi(e);
-        if (k >= 8 && k < c.nwg) c.nwg = k;
-    }
     constexpr int W = kCssWorkers;
     const int64_t per_pass = (int64_t)c.nwg * kCssMaxRows;
     const int P_min = (int)std::max<int64_t>(1, (A.m + per_pass - 1) / per_pass);
@@ -1020,8 +959,7 @@ int css_layout(spmv_plan_s *p, const int64_t *row_ptr, int64_t m, int64_t n, int
     std::vector<int64_t> &roff = CL.roff;  // [nb + 1] into rmap
     std::vector<int32_t> &rmap = CL.rmap;  // block rows in slot order
     int64_t piece_cap = 0;
-    int piece_div = 2;
-    if (const char *d = probe_env("SPMV_CSS_PIECE_DIV")) piece_div = std::max(1, std::atoi(d));
+    constexpr int piece_div = 2;
     bool fitted = false;
     for (c.P = P_min; c.P <= P_min + 1024 && !fitted; ++c.P) {
         const int64_t nb = (int64_t)c.P * c.nwg;
@@ -1163,10 +1101,10 @@ int css_layout(spmv_plan_s *p, const int64_t *row_ptr, int64_t m, int64_t n, int
             moff[(size_t)pb + 1] = (int64_t)merges[(size_t)pb].size() / 3;
         }
     }
-    // list lengths -> physical layout.  Contiguous: list L at woff[L].
-    // Interleaved (default): chunk k (256 entries) of list L of pass p at
-    // pbase + (k * lists_per_pass + L_local) * 256, so at any time all waves of
-    // the chip stream one contiguous band of the entry arrays (measured:
+    // list lengths -> physical layout, interleaved: chunk k (256 entries) of
+    // list L of pass p at pbase + (k * lists_per_pass + L_local) * 256, so at
+    // any time all waves of the chip stream one contiguous band of the entry
+    // arrays (measured against one contiguous run per list:
     // tools/gather_probe.hip e10 vs e13); lists are padded to the longest of
     // the pass with benign entries (col 0, dummy slot, val 0).
     std::vector<int32_t> &wlen = CL.wlen;
@@ -1174,26 +1112,17 @@ int css_layout(spmv_plan_s *p, const int64_t *row_ptr, int64_t m, int64_t n, int
     for (int64_t L = 0; L < nlists; ++L) wlen[(size_t)L] = (int32_t)woff[(size_t)L + 1];
     for (int64_t b = 0; b < nblocks; ++b) moff[b + 1] += moff[b];
     const int64_t lists_per_pass = (int64_t)c.nwg * W;
-    c.interleaved = true;
-    if (const char *e = probe_env("SPMV_CSS_LAYOUT")) c.interleaved = std::atoi(e) != 0;
     int64_t total = 0;
-    if (c.interleaved) {
-        for (int pp = 0; pp < c.P; ++pp) {
-            int64_t kmax = 0;
-            for (int64_t Lq = 0; Lq < lists_per_pass; ++Lq)
-                kmax = std::max<int64_t>(kmax, ((int64_t)wlen[(size_t)(pp * lists_per_pass + Lq)] + 255) / 256);
-            for (int64_t Lq = 0; Lq < lists_per_pass; ++Lq)
-                woff[(size_t)(pp * lists_per_pass + Lq)] = total + Lq * 256;
-            total += kmax * lists_per_pass * 256;
-        }
-        c.chunk_stride = lists_per_pass * 256;
-        woff[(size_t)nlists] = total;
-    } else {
-        woff[0] = 0;
-        for (int64_t L = 0; L < nlists; ++L) woff[(size_t)L + 1] = woff[(size_t)L] + wlen[(size_t)L];
-        total = woff[(size_t)nlists];
-        c.chunk_stride = 256;
+    for (int pp = 0; pp < c.P; ++pp) {
+        int64_t kmax = 0;
+        for (int64_t Lq = 0; Lq < lists_per_pass; ++Lq)
+            kmax = std::max<int64_t>(kmax, ((int64_t)wlen[(size_t)(pp * lists_per_pass + Lq)] + 255) / 256);
+        for (int64_t Lq = 0; Lq < lists_per_pass; ++Lq)
+            woff[(size_t)(pp * lists_per_pass + Lq)] = total + Lq * 256;
+        total += kmax * lists_per_pass * 256;
     }
+    c.chunk_stride = lists_per_pass * 256;
+    woff[(size_t)nlists] = total;
     CL.merge.assign((size_t)std::max<int64_t>(3 * moff[nblocks], 1), 0);
 #pragma omp parallel for schedule(static)
     for (int64_t b = 0; b < nblocks; ++b)
@@ -1233,8 +1162,8 @@ int css_fill_host(spmv_plan_s *p, const HostCsr &A, CssLayout &CL) {
             }
         }
     }
-    // +256 entries: a contiguous list's last chunk may read past the array
-    // (masked lanes); zero col, val -- and slot 0, which masking overrides
+    // +256 entries of slack past the last chunk, as the device fill
+    // allocates (k_css_build.hip): zero col, val and slot
     SPMV_RETURN_IF(plan_upload(p, &c.col, col.data(), total, 256));
     SPMV_RETURN_IF(plan_upload(p, &c.row, slot.data(), total, 256));
     SPMV_RETURN_IF(plan_upload(p, &c.val, val.data(), total, 256));

@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <functional>
@@ -71,7 +72,7 @@ inline int scratch_malloc(T **q, size_t n, const char *what = "") {
 
 // ---- experiment switches ------------------------------------------------
 // The probe build (`make probes`, -DSPMV_PROBES, probes_build/) reads the
-// SPMV_<FORMAT>_* tuning and ablation variables the tools/ scripts set; the
+// variables listed in DESIGN.md §9.1, each through ONE probe_env call; the
 // product library ignores them all, so no stray environment variable can
 // change what spmv_execute computes or how fast it runs.
 inline const char *probe_env(const char *name) {
@@ -89,6 +90,13 @@ inline const char *probe_env(const char *name) {
 inline int launch_dbg(int plan_dbg) {
     if (const char *e = probe_env("SPMV_LAUNCH_DEBUG")) return std::atoi(e);
     return plan_dbg;
+}
+
+// Probe build: SPMV_DIA_GROUP, read by both DIA builders at plan build
+// (DiaDev::group; the product's layout is group 0).
+inline int dia_probe_group() {
+    if (const char *e = probe_env("SPMV_DIA_GROUP")) return std::max(0, std::atoi(e));
+    return 0;
 }
 
 // Placement modes.  AUTO (the default) holds no transient
@@ -148,8 +156,6 @@ constexpr int kCsrBinLanes[kCsrBins] = {1, 2, 4, 8, 16, 32, 64, 256};
 constexpr int kCsrMaxWin = 4096;   // columns of a csr_slabx x window (32 KB of LDS)
 constexpr int kCsrWinGroup = 256;  // rows of one x-window granule (4 waves x 1 slab of 64)
 constexpr int kCsrSlabsPerWave = 1;  // csr_slabx default: a workgroup owns 1 granule (256 rows)
-// CsrDev::win_s index of a workgroup of S = 1, 2 or 4 granules
-constexpr int csr_win_index(int S) { return S == 4 ? 2 : S == 1 ? 0 : 1; }
 struct CsrDev {
     void *row_ptr = nullptr;  // int32 or int64 [m+1]
     bool rp64 = false;
@@ -163,7 +169,7 @@ struct CsrDev {
     int64_t slab_max = 0;     // entries of the widest 64-row slab
     int32_t *win0 = nullptr;  // [ceil(m / kCsrWinGroup)]: first column of each 256-row granule's
     int32_t win = 0;          //   x window; win = the widest window of kCsrSlabsPerWave granules
-    int32_t win_s[3] = {};    //   ... of 1, 2, 4 granules (0: wider than kCsrMaxWin); null: none fits
+                              //   (win0 null: that window is wider than kCsrMaxWin)
     int32_t *bin_rows = nullptr;        // rows of every bin, ascending within a bin
     int64_t bin_off[kCsrBins + 1] = {};  // host: bin b = bin_rows[bin_off[b], bin_off[b+1])
 };
@@ -173,12 +179,8 @@ __host__ __device__ inline int64_t csr_val_halves_entry(int64_t pos) {
     const int64_t r = pos & 255;
     return (pos & ~(int64_t)255) + ((r & 127) >> 1) * 4 + (r >> 7) * 2 + (r & 1);
 }
-// row-group plans store their values in halves (probe build:
-// SPMV_CSR_VAL_PLAIN=1 keeps CSR order, for A/Bs)
-inline bool csr_val_halves_wanted(const CsrDev &c) {
-    if (const char *e = probe_env("SPMV_CSR_VAL_PLAIN")) return c.lanes > 0 && std::atoi(e) == 0;
-    return c.lanes > 0;
-}
+// row-group plans store their values in halves
+inline bool csr_val_halves_wanted(const CsrDev &c) { return c.lanes > 0; }
 
 // Sliced ELL (opt_ell, src/opt_ell.cpp): slices of 64 consecutive rows (one
 // wave); slice s has width w_s (multiple of 4) = max row length in the slice
@@ -195,8 +197,6 @@ struct EllDev {
     double *val = nullptr;
     int max_width = 0;
     int64_t slots = 0;             // stored slots of the ELL part (HYB / JDS: without the overflow)
-    int unroll = 2;  // quads per lane per iteration (SPMV_ELL_UNROLL, internal;
-                     // 2 beat 4 by 28 % at config 4, 5 % at config 2)
 };
 
 // HYB overflow: rows whose length exceeds K keep entries K.. in a CSR over
@@ -234,9 +234,6 @@ struct SsDev {
     double *val = nullptr;
     uint32_t *flags = nullptr;   // [n_tiles][words][64]
     int32_t *win = nullptr;      // [n_tiles][2]: x window (first column, length; 0 = none)
-    int kernel = 1;              // 1 = ss_stream_kernel, 0 = ss_tile_kernel (SIGMA <= 32)
-    int pf = 2;                  // ss_stream_kernel: quads loaded ahead
-    bool stage = true;           // ss_stream_kernel: finished rows staged in LDS, stored after the stream
     int32_t *tile_ord = nullptr;
     double *ht = nullptr;        // scratch [n_tiles][2]: head partial, tail partial (one store per tile)
     int32_t *tail_ord = nullptr; // [n_tiles] plan-time: ordinal of the tile's last row start, -1 = none
@@ -270,9 +267,7 @@ struct DiaDev {
     std::vector<int32_t> off_host;
     double *val = nullptr;   // [n_diags * mp]
     int64_t mp = 0;          // m rounded up to kDiaBlockRows
-    int dbg = 0;             // SPMV_DIA_DEBUG (internal): 1 = x from global memory, no LDS window
-    int group = 0;           // > 0: value blocks interleaved per group of blocks (k_dia.hip)
-    int lds_kb = -1;         // SPMV_DIA_LDS_KB (probe): LDS per workgroup (0: window only); -1: kDiaLdsKb
+    int group = 0;           // > 0: value blocks interleaved per group of blocks (k_dia.hip; dia_probe_group)
     int placement = 0;       // SPMV_PLACEMENT_* used for val
     std::vector<float> placement_ms;
 };
@@ -289,8 +284,8 @@ struct CssDev {
     int nwg = 0, R = 0, P = 0, S = 0, slab_shift = 17, lag = 2, pace_all = 0;
     int64_t *woff = nullptr;    // physical start of each list's chunk 0
     int32_t *wlen = nullptr;    // entries of each list
-    int64_t chunk_stride = 256; // entries between a list's consecutive 256-entry chunks
-    bool interleaved = true;    // chunks of all lists of a pass interleaved
+    int64_t chunk_stride = 256; // entries between a list's consecutive 256-entry chunks (all lists
+                                //   of a pass interleaved: lists per pass * 256)
     int64_t *bstart = nullptr;  // [P*nwg + 1] offsets of each (pass, workgroup) block's rows in rmap
     int32_t *rmap = nullptr;    // block rows in slot order; null = identity (contiguous blocks)
     int64_t *moff = nullptr;    // [P*nwg + 1] merge-triple offsets per block
@@ -639,7 +634,6 @@ void csr_finish_info(spmv_plan_s *p);
 int auto_ss_sigma(double mean_row);
 void ss_tile_windows(const int32_t *col, int64_t nnz, int64_t n_tiles, int sigma, std::vector<int32_t> &win);
 void ss_finish_info(spmv_plan_s *p);
-void ss_probe_options(SsDev &s);
 int ss_plan_tail_ord(spmv_plan_s *p);
 
 // end of one phase of a multi-kernel launch (no-op unless profiling)

@@ -298,7 +298,7 @@ static int csr_x_windows_device(spmv_plan_s *p, const int64_t *d_rp) {
 int build_csr_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o) {
     CsrDev &c = p->csr;
     const hipStream_t st = p->stream;
-    c.rp64 = p->nnz >= (int64_t)INT32_MAX - 64 || o.csr_row_ptr64 != 0 || probe_env("SPMV_CSR_FORCE_RP64");
+    c.rp64 = p->nnz >= (int64_t)INT32_MAX - 64 || o.csr_row_ptr64 != 0;
     SPMV_RETURN_IF(p->arena.alloc(&c.row_ptr, (c.rp64 ? 8 : 4) * (size_t)(p->m + 1)));
     if (c.rp64) SPMV_HIP_TRY(hipMemcpyAsync(c.row_ptr, A.d_rp, 8 * (size_t)(p->m + 1), hipMemcpyDeviceToDevice, st));
     else
@@ -336,7 +336,6 @@ int build_ss_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o) {
         set_error("ss_sigma must be one of 4,8,12,16,20,24,32,48,64");
         return SPMV_ERROR_INVALID_VALUE;
     }
-    ss_probe_options(s);
     const int W = ss_flag_words(s.sigma);
     const int64_t T = 64 * (int64_t)s.sigma;
     s.n_tiles = (nnz + T - 1) / T;

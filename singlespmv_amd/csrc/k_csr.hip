@@ -29,8 +29,6 @@
 // in the store epilogue, csr_slab_store<AB> / csr_store_row<ADD, AB>; the
 // row's writer loads its y0 before the row is streamed); alpha and beta are
 // arguments of the twins only.
-// csr_vec4<L> (a row per group, no slabs: the round-3 kernel) is compiled
-// into the probe build only, for A/Bs (SPMV_LAUNCH_CSR=0).
 //
 // Algorithmic bytes per row: 12*nnz_i + rp bytes + 8 (y) and the
 // x gathers (8*n total, counted once).
@@ -96,26 +94,12 @@ __device__ __forceinline__ void csr_store_row(double *__restrict__ y, const int3
     }
 }
 
-template <int L, typename RP>
-__global__ __launch_bounds__(256) void csr_vec4_kernel(int64_t m,
-                                                       const RP *__restrict__ rp,
-                                                       const int32_t *__restrict__ col,
-                                                       const double *__restrict__ val,
-                                                       const double *__restrict__ x,
-                                                       double *__restrict__ y, bool vh) {
-    const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t row = gtid / L;
-    const int lane = threadIdx.x & (L - 1);
-    if (row >= m) return;  // whole groups exit together (L | 256)
-    const double acc = group_sum<L>(csr_row_sum<L>(rp[row], rp[row + 1], lane, col, val, x, vh));
-    if (lane == 0) y[row] = acc;
-}
-
 // ---- the slab batch (csr_slab2, csr_slabx) ---------------------------------
 // A wave owns a slab of 64 consecutive rows and sums it in L steps of R = 64 /
 // L rows, row (st R + g) of the slab by lane group g in step st, exactly as
 // csr_row_sum<L> and group_sum<L> sum it (same chunks, same order, same
-// butterfly: both kernels and csr_vec4<L> give bit-identical y).  A batch is
+// butterfly: both kernels and round 3's row-per-group csr_vec4<L> gave
+// bit-identical y).  A batch is
 // U steps whose col / val loads are issued before their x reads.  A
 // long-lived wave replaces 64 / (256 / L) short ones and y leaves in one
 // coalesced store per slab (config 4, same plans: csr_vec4<16> 2.82 -> 2.48
@@ -580,74 +564,41 @@ static int launch_adaptive(const spmv_plan_s *p, const int64_t *bin_off, const i
 
 // launch-time shape of the row-parallel CSR kernels: csr_slabx where the plan
 // has x windows (banded rows), else csr_slab2, with U = min(4, L) steps per
-// batch.  Config 4 (16 lanes), same plans: csr_vec4 2.80-2.87, csr_slab2 U =
-// 1 / 2 / 4 / 8 2.64 / 2.55 / 2.49 / 2.54 ms, csr_slabx U = 4 2.41-2.54 ms
-// against csr_slab2's 2.54-2.62 on the same plans; config 2 (gather-bound)
-// within 1 % (profiles/round4/probe/c4_csr_slab2_first.jsonl,
-// c4_csr_slabx_s1.jsonl, c4_csr_slabx_pairs.jsonl, c2_csr_slab2_slabx.jsonl).
-// The probe build reads SPMV_LAUNCH_CSR (0: csr_vec4, the round-3 kernel; 2:
-// csr_slab2), SPMV_LAUNCH_CSR_U and SPMV_LAUNCH_CSR_LDS_KB at every launch, so
-// variants are A/B'd on one plan's memory.
-struct CsrLaunch {
-    int slab = 3;    // 3: csr_slabx where the plan has x windows, else csr_slab2; 2: csr_slab2;
-                     // 0: csr_vec4 (probe A/B)
-    int u = 4;       // slab: steps whose loads are issued together
-    size_t lds = 0;  // dynamic LDS per workgroup (caps workgroups per CU; probe)
-};
-#ifdef SPMV_PROBES
-static CsrLaunch csr_launch_shape() {
-    CsrLaunch s;
-    if (const char *e = probe_env("SPMV_LAUNCH_CSR")) s.slab = std::atoi(e);
-    if (const char *e = probe_env("SPMV_LAUNCH_CSR_U")) s.u = std::atoi(e);
-    if (const char *e = probe_env("SPMV_LAUNCH_CSR_LDS_KB")) s.lds = (size_t)std::atoi(e) * 1024;
-    return s;
-}
-#endif
+// batch.  Config 4 (16 lanes), same plans: csr_vec4 (round 3's row per group)
+// 2.80-2.87, csr_slab2 U = 1 / 2 / 4 / 8 2.64 / 2.55 / 2.49 / 2.54 ms,
+// csr_slabx U = 4 2.41-2.54 ms against csr_slab2's 2.54-2.62 on the same
+// plans; config 2 (gather-bound) within 1 % (round 4 A/Bs,
+// profiles/round4/probe/c4_csr_slab2_first.jsonl, c4_csr_slabx_s1.jsonl,
+// c4_csr_slabx_pairs.jsonl, c2_csr_slab2_slabx.jsonl).
+constexpr int kCsrBatchSteps = 4;  // slab: steps whose loads are issued together
 
-template <int L, typename RP, int U>
-static void launch_slab_u(const spmv_plan_s *p, int kind, size_t lds, const double *x, double *y, const Axpby *ab) {
-    constexpr int UU = U < L ? U : L;
+template <int L, typename RP>
+static void launch_slab(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab) {
+    constexpr int UU = kCsrBatchSteps < L ? kCsrBatchSteps : L;
+    constexpr int S = kCsrSlabsPerWave;  // granules (64-row slabs per wave) per workgroup
     const int64_t waves = (p->m + 63) / 64;
     const CsrDev &c = p->csr;
-    if (kind >= 3 && c.win0) {  // x window in LDS, stream one batch ahead
-        // S granules (64-row slabs per wave) per workgroup: kCsrSlabsPerWave;
-        // probe build: SPMV_LAUNCH_CSR_S = 1, 2 or 4 where that window fits
-        int S = kCsrSlabsPerWave;
-#ifdef SPMV_PROBES
-        if (const char *e = probe_env("SPMV_LAUNCH_CSR_S")) S = std::atoi(e);
-        if (!c.win_s[csr_win_index(S)]) S = kCsrSlabsPerWave;
-#endif
-        const int32_t win = c.win_s[csr_win_index(S)];
-        const size_t wl = std::max(lds, sizeof(double) * (size_t)win);
+    if (c.win0) {  // x window in LDS, stream one batch ahead
         const unsigned grid = (unsigned)((p->m + 256 * S - 1) / (256 * S));
         auto go = [&](auto kern, auto... ab_args) {
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), wl, p->stream, p->m, (const RP *)c.row_ptr, c.col, c.val,
-                               x, y, c.win0, win, p->n, c.val_halves, ab_args...);
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), sizeof(double) * (size_t)c.win, p->stream, p->m,
+                               (const RP *)c.row_ptr, c.col, c.val, x, y, c.win0, c.win, p->n, c.val_halves,
+                               ab_args...);
         };
         // 32-bit offsets span the wave's S slabs (off32 is per single slab)
-        auto go_s = [&](auto sc) {
-            constexpr int SS = decltype(sc)::value;
-            const bool o32 = c.off32 && (SS == 1 || (int64_t)SS * c.slab_max + 512 < ((int64_t)1 << 28));
-            if (ab) {
-                if (o32) go(csr_slabx_axpby_kernel<L, RP, UU, SS, true>, ab->alpha, ab->beta);
-                else go(csr_slabx_axpby_kernel<L, RP, UU, SS, false>, ab->alpha, ab->beta);
-            } else if (o32) {
-                go(csr_slabx_kernel<L, RP, UU, SS, true>);
-            } else {
-                go(csr_slabx_kernel<L, RP, UU, SS, false>);
-            }
-        };
-#ifdef SPMV_PROBES
-        if (S == 1) go_s(std::integral_constant<int, 1>{});
-        else if (S == 4) go_s(std::integral_constant<int, 4>{});
-        else go_s(std::integral_constant<int, 2>{});
-#else
-        go_s(std::integral_constant<int, kCsrSlabsPerWave>{});
-#endif
+        const bool o32 = c.off32 && (S == 1 || (int64_t)S * c.slab_max + 512 < ((int64_t)1 << 28));
+        if (ab) {
+            if (o32) go(csr_slabx_axpby_kernel<L, RP, UU, S, true>, ab->alpha, ab->beta);
+            else go(csr_slabx_axpby_kernel<L, RP, UU, S, false>, ab->alpha, ab->beta);
+        } else if (o32) {
+            go(csr_slabx_kernel<L, RP, UU, S, true>);
+        } else {
+            go(csr_slabx_kernel<L, RP, UU, S, false>);
+        }
         return;
     }
     auto go = [&](auto kern, auto... ab_args) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)((waves + 3) / 4)), dim3(256), lds, p->stream, p->m,
+        hipLaunchKernelGGL(kern, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, p->stream, p->m,
                            (const RP *)c.row_ptr, c.col, c.val, x, y, c.val_halves, ab_args...);
     };
     if (ab) {
@@ -660,31 +611,10 @@ static void launch_slab_u(const spmv_plan_s *p, int kind, size_t lds, const doub
     }
 }
 
-// The product instantiates only the default shape (CsrLaunch{}: slab 3, U =
-// 4, S = kCsrSlabsPerWave); the probe build adds csr_vec4 and U / S / LDS
-// variants, read at every launch.
 template <int L, typename RP>
 static int launch_csr_t(const spmv_plan_s *p, int64_t nrows, const double *x, double *y, const Axpby *ab) {
-    const int64_t threads = nrows * L;
-    const int64_t blocks = (threads + 255) / 256;
-    if (blocks == 0) return SPMV_SUCCESS;
-#ifdef SPMV_PROBES
-    const CsrLaunch sh = ab ? CsrLaunch{} : csr_launch_shape();  // the axpby epilogue: the product's shape only
-    if (sh.slab) {
-        switch (sh.u) {
-            case 1: launch_slab_u<L, RP, 1>(p, sh.slab, sh.lds, x, y, nullptr); break;
-            case 2: launch_slab_u<L, RP, 2>(p, sh.slab, sh.lds, x, y, nullptr); break;
-            case 8: launch_slab_u<L, RP, 8>(p, sh.slab, sh.lds, x, y, nullptr); break;
-            default: launch_slab_u<L, RP, 4>(p, sh.slab, sh.lds, x, y, ab);
-        }
-    } else {
-        hipLaunchKernelGGL((csr_vec4_kernel<L, RP>), dim3((unsigned)blocks), dim3(256), sh.lds, p->stream, nrows,
-                           (const RP *)p->csr.row_ptr, p->csr.col, p->csr.val, x, y, p->csr.val_halves);
-    }
-#else
-    constexpr CsrLaunch sh{};
-    launch_slab_u<L, RP, sh.u>(p, sh.slab, sh.lds, x, y, ab);
-#endif
+    if (nrows == 0) return SPMV_SUCCESS;
+    launch_slab<L, RP>(p, x, y, ab);
     SPMV_HIP_TRY(hipGetLastError());
     return SPMV_SUCCESS;
 }

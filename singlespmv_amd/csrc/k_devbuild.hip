@@ -218,7 +218,6 @@ __global__ __launch_bounds__(256) void coo_rows_kernel(const int64_t *__restrict
 // the ELL part (cap, order: JDS) of a plan from a device CSR
 int ell_fill_device(spmv_plan_s *p, const DevCsr &A, int cap, const int32_t *h_order, const int32_t *d_order) {
     EllDev &e = p->ell;
-    if (const char *u = probe_env("SPMV_ELL_UNROLL")) e.unroll = std::atoi(u);
     e.n_slices = (A.m + 63) / 64;
     std::vector<int64_t> off;
     const int maxw = ell_slice_offsets(A.h_rp, A.m, cap, h_order, off);
@@ -316,9 +315,7 @@ int build_dia_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o) {
     d.off_host = offs;
     d.mp = (A.m + kDiaBlockRows - 1) / kDiaBlockRows * kDiaBlockRows;
     const int64_t slots = (int64_t)d.n_diags * d.mp;
-    if (const char *e = probe_env("SPMV_DIA_GROUP")) d.group = std::max(0, std::atoi(e));
-    if (const char *e = probe_env("SPMV_DIA_DEBUG")) d.dbg = std::atoi(e);
-    if (const char *e = probe_env("SPMV_DIA_LDS_KB")) d.lds_kb = std::atoi(e);
+    d.group = dia_probe_group();
     SPMV_RETURN_IF(plan_upload(p, &d.off, offs.data(), d.n_diags));
     // the value buffer as build_dia places it: AUTO puts >= 256 MB straight
     // into 2-MB VMM handles at a 1-GB-aligned VA
@@ -327,7 +324,7 @@ int build_dia_device(spmv_plan_s *p, const DevCsr &A, const spmv_options_t &o) {
     SPMV_RETURN_IF(placement_mode_check(oo.placement));
     if (oo.placement == SPMV_PLACEMENT_AUTO)
         oo.placement = vbytes >= kDiaVmmMinBytes ? SPMV_PLACEMENT_VMM : SPMV_PLACEMENT_PLAIN;
-    const bool vmm_now = oo.placement == SPMV_PLACEMENT_VMM && !probe_env("SPMV_PLACEMENT_MODE");
+    const bool vmm_now = oo.placement == SPMV_PLACEMENT_VMM;
     if (vmm_now) {
         void *q = nullptr;
         SPMV_RETURN_IF(p->arena.alloc_vmm(&q, vbytes, kVmmChunk, p->device, kVmmAlign));

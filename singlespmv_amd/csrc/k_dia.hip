@@ -244,9 +244,9 @@ int launch_dia(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab
     // 2 M rows (1 GB) 0.163 vs 0.159; 6 M rows (3 GB) 0.486 vs 0.466
     // (profiles/round4/probe/dia_cap_{200k,2m,6m}.jsonl)
     const bool big = (size_t)d.n_diags * (size_t)d.mp * sizeof(double) >= kDiaVmmMinBytes;
-    int kb = d.lds_kb >= 0 ? d.lds_kb : (big ? kDiaLdsKb : 0);
-    if (const char *e = probe_env("SPMV_LAUNCH_DIA_LDS_KB")) kb = std::atoi(e);
-    const int dbg = launch_dbg(d.dbg);
+    int kb = big ? kDiaLdsKb : 0;
+    if (const char *e = probe_env("SPMV_LAUNCH_DIA_LDS_KB")) kb = std::atoi(e);  // probe: occupancy A/B
+    const int dbg = launch_dbg(0);  // probe: bit 0 = x from global memory, no LDS window
     const bool fits = g.win <= kDiaMaxWin;
     auto go = [&](auto kernel, bool ldsx, auto... ab_args) {
         const size_t lds = ldsx ? std::max(sizeof(double) * (size_t)g.win, (size_t)kb * 1024) : 0;
@@ -259,12 +259,6 @@ int launch_dia(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab
         SPMV_HIP_TRY(hipGetLastError());
         return SPMV_SUCCESS;
     }
-#ifdef SPMV_PROBES
-    if (fits && (dbg & 4)) go(dia_kernel<4, true>, true);  // probe A/B: 4 (dbg 4) / 16 (dbg 8) diagonals in flight per lane
-    else if (fits && (dbg & 8)) go(dia_kernel<16, true>, true);
-    else if (fits && (dbg & 2)) go(dia_kernel<8, true, 1>, true);  // probe A/B: ordinary y stores
-    else
-#endif
     if (fits && !(dbg & 1)) go(dia_kernel<8, true>, true);
     else go(dia_kernel<8, false>, false);
     SPMV_HIP_TRY(hipGetLastError());

@@ -4,11 +4,7 @@
 // compute -> calibrate -> tail) with a fused, deterministic, idempotent
 // wave64 design.
 //
-// The product launches ss_stream_kernel (below); ss_tile_kernel, its
-// all-loads-first twin, is compiled into the probe build only (`make probes`,
-// SPMV_SS_KERNEL=0), like the stream kernel's non-default PF / stage / window
-// instances.
-// The tile, common to both: one wave = 64 lanes x SIGMA nnz.  Lane l
+// The tile: one wave = 64 lanes x SIGMA nnz.  Lane l
 // owns SIGMA consecutive nnz (see SsDev layout: every wave load instruction is
 // 1 KiB contiguous -- col as 4 ints per lane, val as two 1-KiB halves of 2
 // doubles per lane, like ELL's values).  Products never touch memory (no val_buf: opt_ss's extra
@@ -93,110 +89,9 @@ __device__ __forceinline__ void ss_tile_end(int lane, int64_t tile, uint64_t bal
     if (a) *a = v;
 }
 
-#ifdef SPMV_PROBES  // round 4's kernel: probe build only (launch_ss_probe)
-template <int SIGMA, bool WIN>
-__global__ __launch_bounds__(256) void ss_tile_kernel(
-    int64_t n_tiles, const int32_t *__restrict__ col, const double *__restrict__ val,
-    const uint32_t *__restrict__ flags, const int32_t *__restrict__ tile_ord,
-    const int32_t *__restrict__ nzrow, int64_t n_nonempty, const double *__restrict__ x,
-    double *__restrict__ y, double *__restrict__ ht) {
-    static_assert(SIGMA % 4 == 0 && SIGMA <= 32, "sigma");
-    constexpr int Q = SIGMA / 4;
-    const int64_t tile = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (tile >= n_tiles) return;  // wave-uniform
-    const int64_t base = tile * 64 * SIGMA;
-    const uint32_t f = flags[tile * 64 + lane];
-    const int32_t *cp = col + base + lane * 4;
-    const double *vp = val + base + lane * 2;  // entries k%4 < 2 of step k/4, then k%4 >= 2 128 later
-
-    i32x4 c[Q];
-    f64x2 a[Q], b[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        c[q] = ld_stream4(cp + q * 256);
-        a[q] = ld_stream2(vp + q * 256);
-        b[q] = ld_stream2(vp + q * 256 + 128);
-    }
-    double g[SIGMA];
-    bool gathered = false;
-    if constexpr (WIN) {
-        // the tile's column range; when it fits kSsWin, x comes through a
-        // per-wave LDS window (coalesced loads, then LDS reads) instead of
-        // SIGMA gathers that each touch up to 64 lines
-        __shared__ double xs[4][kSsWin];
-        int lo = INT32_MAX, hi = -1;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            lo = min(lo, min(min(c[q].x, c[q].y), min(c[q].z, c[q].w)));
-            hi = max(hi, max(max(c[q].x, c[q].y), max(c[q].z, c[q].w)));
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            lo = min(lo, __shfl_xor(lo, o, 64));
-            hi = max(hi, __shfl_xor(hi, o, 64));
-        }
-        lo = __builtin_amdgcn_readfirstlane(lo);
-        hi = __builtin_amdgcn_readfirstlane(hi);
-        if (hi - lo < kSsWin) {  // wave-uniform
-            const int wv = threadIdx.x >> 6;
-            for (int i = lane; i <= hi - lo; i += 64) xs[wv][i] = ld_x(x, lo + i);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-            for (int q = 0; q < Q; ++q) {
-                g[4 * q + 0] = xs[wv][c[q].x - lo];
-                g[4 * q + 1] = xs[wv][c[q].y - lo];
-                g[4 * q + 2] = xs[wv][c[q].z - lo];
-                g[4 * q + 3] = xs[wv][c[q].w - lo];
-            }
-            gathered = true;
-        }
-    }
-    if (!gathered) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            g[4 * q + 0] = ld_x(x, c[q].x);
-            g[4 * q + 1] = ld_x(x, c[q].y);
-            g[4 * q + 2] = ld_x(x, c[q].z);
-            g[4 * q + 3] = ld_x(x, c[q].w);
-        }
-    }
-
-    const int pc = __builtin_popcount(f);
-    const int incl = wave_inclusive_sum(pc, lane);
-    const int64_t ord0 = (int64_t)tile_ord[tile] + (incl - pc);  // this lane's first start
-
-    double run = 0.0, head_l = 0.0;
-    int seen = 0;
-#pragma unroll
-    for (int k = 0; k < SIGMA; ++k) {
-        if ((f >> k) & 1u) {
-            if (seen == 0) head_l = run;
-            else ss_store(y, nzrow, n_nonempty, ord0 + seen - 1, run);
-            run = 0.0;
-            ++seen;
-        }
-        const double v = (k & 2) ? ((k & 1) ? b[k >> 2].y : b[k >> 2].x)
-                                 : ((k & 1) ? a[k >> 2].y : a[k >> 2].x);
-        run = madd(v, g[k], run);
-    }
-
-    const bool has = f != 0u;
-    const double S = wave_seg_scan(run, has, lane);  // open-segment sum at lane end
-    double C = __shfl_up(S, 1, 64);
-    if (lane == 0) C = 0.0;
-    const uint64_t ball = __ballot(has);
-    const bool started_before = (ball & ((1ull << lane) - 1ull)) != 0ull;
-    const double tot = __dadd_rn(C, head_l);
-    if (has && started_before) ss_store(y, nzrow, n_nonempty, ord0 - 1, tot);
-    ss_tile_end(lane, tile, ball, tot, S, 0, nullptr, 0, nzrow, n_nonempty, y, ht);
-}
-#endif
-
 // ss_stream_kernel<SIGMA, WIN, PF>: the same tile, sums and hand-off as
-// ss_tile_kernel (bit-identical y), streamed: the quads of a lane are loaded
+// round 4's all-loads-first ss_tile_kernel (bit-identical y; its A/Bs:
+// profiles/round5/README.md), streamed: the quads of a lane are loaded
 // PF ahead of the quad being summed (sched_barrier-fenced stages), so a lane
 // holds PF + 1 quads instead of all SIGMA entries -- SIGMA up to 64 (two flag
 // words per lane) at the register cost of SIGMA 12.  The x window of a tile is
@@ -382,60 +277,11 @@ int ss_plan_tail_ord(spmv_plan_s *p) {
     return SPMV_SUCCESS;
 }
 
-#ifdef SPMV_PROBES
-// Probe build only (`make probes`): the round-4 all-loads-first kernel
-// (SPMV_LAUNCH_SS = 0 / SPMV_SS_KERNEL = 0), the other prefetch depths
-// (SPMV_LAUNCH_SS_PF 1 / 4), unstaged rows (SPMV_LAUNCH_SS_STAGE = 0), no x
-// window (SPMV_LAUNCH_SS_WIN = 0) and a dynamic-LDS cap on workgroups per CU
-// (SPMV_LAUNCH_SS_LDS_KB).  None of these instances is in the product library.
-template <int SIGMA>
-static void launch_ss_probe(const spmv_plan_s *p, const double *x, double *y) {
-    const SsDev &s = p->ss;
-    const int64_t blocks = (s.n_tiles + 3) / 4;
-    int kind = SIGMA > 32 && s.kernel == 0 ? 1 : s.kernel, pf = s.pf;
-    size_t lds = 0;
-    bool win = true, stage = s.stage;
-    if (const char *v = probe_env("SPMV_LAUNCH_SS_STAGE")) stage = std::atoi(v) != 0;
-    if (const char *v = probe_env("SPMV_LAUNCH_SS_LDS_KB")) lds = (size_t)std::atoi(v) * 1024;
-    if (const char *v = probe_env("SPMV_LAUNCH_SS")) kind = SIGMA > 32 && std::atoi(v) == 0 ? 1 : std::atoi(v);
-    if (const char *v = probe_env("SPMV_LAUNCH_SS_PF")) pf = std::atoi(v);
-    if (const char *v = probe_env("SPMV_LAUNCH_SS_WIN")) win = std::atoi(v) != 0;
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, p->stream, s.n_tiles, s.col, s.val, s.flags,
-                           s.tile_ord, s.win, s.nzrow, s.n_nonempty, x, y, s.ht);
-    };
-    if (kind == 0 && SIGMA <= 32) {
-        constexpr int S0 = SIGMA <= 32 ? SIGMA : 32;
-        if (win)
-            hipLaunchKernelGGL((ss_tile_kernel<S0, true>), dim3((unsigned)blocks), dim3(256), lds, p->stream,
-                               s.n_tiles, s.col, s.val, s.flags, s.tile_ord, s.nzrow, s.n_nonempty, x, y, s.ht);
-        else
-            hipLaunchKernelGGL((ss_tile_kernel<S0, false>), dim3((unsigned)blocks), dim3(256), lds, p->stream,
-                               s.n_tiles, s.col, s.val, s.flags, s.tile_ord, s.nzrow, s.n_nonempty, x, y, s.ht);
-        return;
-    }
-    win = win && s.win;
-    auto pick = [&](auto pfc) {
-        constexpr int P = decltype(pfc)::value;
-        if (stage) win ? go(ss_stream_kernel<SIGMA, true, P, true>) : go(ss_stream_kernel<SIGMA, false, P, true>);
-        else win ? go(ss_stream_kernel<SIGMA, true, P, false>) : go(ss_stream_kernel<SIGMA, false, P, false>);
-    };
-    switch (pf) {
-        case 1: pick(std::integral_constant<int, 1>{}); break;
-        case 4: pick(std::integral_constant<int, 4>{}); break;
-        default: pick(std::integral_constant<int, 2>{});
-    }
-}
-#endif
-
 // The product launch: the streamed kernel, 2 quads ahead, finished rows
 // staged in LDS, x through the plan's per-tile windows (when the plan has any)
 // -- two instances per SIGMA.
 template <int SIGMA>
 static void launch_ss_t(const spmv_plan_s *p, const double *x, double *y) {
-#ifdef SPMV_PROBES
-    launch_ss_probe<SIGMA>(p, x, y);
-#else
     const SsDev &s = p->ss;
     const dim3 grid((unsigned)((s.n_tiles + 3) / 4));
     if (s.win)
@@ -444,7 +290,6 @@ static void launch_ss_t(const spmv_plan_s *p, const double *x, double *y) {
     else
         hipLaunchKernelGGL((ss_stream_kernel<SIGMA, false, 2, true>), grid, dim3(256), 0, p->stream, s.n_tiles, s.col,
                            s.val, s.flags, s.tile_ord, s.win, s.nzrow, s.n_nonempty, x, y, s.ht);
-#endif
 }
 
 int launch_ss(const spmv_plan_s *p, const double *x, double *y) {

@@ -51,7 +51,48 @@ def test_product_library_reads_no_experiment_switch():
 def test_probe_build_reads_them():
     subprocess.check_call(["make", "-s", "-j8", "probes"], cwd=ROOT)
     s = _strings(os.path.join(ROOT, "probes_build", "libspmv_hip.so"))
-    assert all(v in s for v in ("SPMV_BIN_DEBUG", "SPMV_CSS_DEBUG", "SPMV_DIA_DEBUG", "SPMV_PLACEMENT_MODE"))
+    assert all(v in s for v in ("SPMV_BIN_DEBUG", "SPMV_CSS_DEBUG", "SPMV_DIA_GROUP", "SPMV_VMM_CHUNK_MB"))
+
+
+# the switches the probe build still reads: DESIGN.md §9.6 has one row for each
+LIVE_PROBE_VARS = ["SPMV_BIN_DEBUG", "SPMV_BIN_REUSE", "SPMV_BIN_SB", "SPMV_BIN_MUL_PERM", "SPMV_BIN_HOST_BUILD",
+                   "SPMV_VMM_CHUNK_MB", "SPMV_CSS_DEBUG", "SPMV_DIA_GROUP", "SPMV_LAUNCH_DEBUG",
+                   "SPMV_LAUNCH_DIA_LDS_KB", "SPMV_LAUNCH_DIA_MULTI_LDSX", "SPMV_LAUNCH_DIA_MULTI_LDS_KB",
+                   "SPMV_LAUNCH_AXPBY_GENERIC"]
+
+
+def test_probe_switches_are_the_documented_ones():
+    """The variables read through probe_env("...") in the sources are exactly
+    LIVE_PROBE_VARS, each has its row in DESIGN.md's table of probe-build
+    switches, and the probe build holds every name."""
+    read = set()
+    for f in sorted(os.listdir(CSRC)):
+        read |= set(re.findall(r'probe_env\("([A-Z0-9_]+)"\)', open(os.path.join(CSRC, f)).read()))
+    assert read == set(LIVE_PROBE_VARS), sorted(read ^ set(LIVE_PROBE_VARS))
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    table = design[design.index("Probe-build switches"):]
+    rows = set(re.findall(r"^\| `(SPMV_[A-Z0-9_]+)` \|", table, flags=re.M))
+    assert rows == set(LIVE_PROBE_VARS), sorted(rows ^ set(LIVE_PROBE_VARS))
+    subprocess.check_call(["make", "-s", "-j8", "probes"], cwd=ROOT)
+    s = _strings(os.path.join(ROOT, "probes_build", "libspmv_hip.so"))
+    assert all(v in s for v in LIVE_PROBE_VARS), [v for v in LIVE_PROBE_VARS if v not in s]
+
+
+# exported for tools/ only, not part of the public header: the BIN product
+# buffer and the scattered-line write probe (tools/placement_probe.py), the
+# CSS per-wave timestamps (what SPMV_CSS_DEBUG & 32 writes)
+UNDECLARED_EXPORTS = {"spmv_bin_prod", "spmv_line_write_probe", "spmv_css_timestamps"}
+
+
+def test_product_library_exports_only_declared_functions():
+    """Every spmv_* dynamic symbol of the product library is declared in
+    include/spmv_hip.h, apart from the three tool hooks above."""
+    out = subprocess.check_output(["nm", "-D", "--defined-only", os.path.join(ROOT, "singlespmv_amd", "libspmv_hip.so")],
+                                  text=True)
+    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("spmv_")}
+    declared = set(re.findall(r"\b(spmv_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", "spmv_hip.h")).read()))
+    assert exported, "no spmv_* symbol exported"
+    assert exported - declared == UNDECLARED_EXPORTS, sorted((exported - declared) ^ UNDECLARED_EXPORTS)
 
 
 def test_product_library_holds_no_probe_kernel_instances():

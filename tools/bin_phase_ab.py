@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """In-process A/B of BIN plan variants, Mul and Sum timed separately.
 
-Each variant is a set of probe-build environment switches read at plan build
-(SPMV_BIN_*; run with SPMV_HIP_LIBRARY=probes_build/libspmv_hip.so); every
+Each variant is a set of plan options and probe-build environment switches
+read at plan build (SPMV_BIN_DEBUG, SPMV_BIN_REUSE, SPMV_BIN_SB,
+SPMV_DIA_GROUP, ...; run with SPMV_HIP_LIBRARY=probes_build/libspmv_hip.so); every
 plan of the process is built from the same CSR, then the plans are profiled
 in interleaved rounds (cdna_hip_programming.md rule 24).  One JSON line per
 (round, variant).
 
   SPMV_HIP_LIBRARY=probes_build/libspmv_hip.so python tools/bin_phase_ab.py \
-      --variants 'base:;ld16:SPMV_BIN_DEBUG=1024' --rows 10000000
+      --variants 'base:;burst:SPMV_BIN_DEBUG=262144' --rows 10000000 \
+      --launch-variants 'dma:;regs:SPMV_LAUNCH_DEBUG=16777216'
 """
 import argparse
 import itertools

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Summarise a tools/profile_round.sh output directory into profiles/<tag>/.
+"""Summarise a directory of rocprofv3 passes over `bench.py --full --no-cpu`
+(trace/: --kernel-trace --stats; pmc_fetch/, pmc_write/: one --pmc counter
+each; bench_*.json: the bench line of each pass) into profiles/<tag>/.
 
 Writes
   profiles/<tag>/kernel_stats.csv      (rocprofv3 --kernel-trace --stats)
