@@ -82,7 +82,9 @@ extern "C" {
  * (spmv_execute_multi, spmv_time_multi, spmv_multi_path) are new functions
  * and change no struct: the version stays 3.  So do the value-refresh entry
  * points (spmv_plan_update_prepare, spmv_plan_update_values) and the BLAS form
- * (spmv_execute_axpby, spmv_time_axpby, spmv_axpby_path).  Callers may
+ * (spmv_execute_axpby, spmv_time_axpby, spmv_axpby_path) and the execute
+ * with dot products (spmv_execute_dot, spmv_time_dot, spmv_dot_path, with the
+ * flags SPMV_W_DEVICE and SPMV_DOTS_DEVICE).  Callers may
  * check spmv_api_version() == SPMV_HIP_API_VERSION once at startup; the
  * structs are only ever filled by spmv_options_default / spmv_plan_info of a
  * library with the same version. */
@@ -549,6 +551,86 @@ int spmv_time_axpby(spmv_plan_t plan, double alpha, const double *x_dev,
 /* *fused = 1: the plan's kernel applies alpha and beta in its store epilogue;
  * 0: generic path.  A check and a documentation aid, like spmv_multi_path. */
 int spmv_axpby_path(spmv_plan_t plan, int32_t *fused);
+
+/* ---- execute with fused dot products: y = A x, w . y and y . y --------------
+ * y = A * x, and from the same pass
+ *   dots[0] = sum_r w[r] * y[r]   (w: m doubles; NULL: dots[0] = +0.0, nothing read)
+ *   dots[1] = sum_r y[r] * y[r]
+ * -- the inner products a Krylov iteration takes right after its SpMV (CG's
+ * p . Ap, BiCGStab's t . s and t . t, the ||Av||^2 of GMRES and Lanczos),
+ * without reading y back in two more launches.
+ *
+ * Results.  y[r] is, bit for bit, what spmv_execute gives on this plan (COO:
+ * within its atomics' order).  t_r = dmul_rn(w[r], y[r]) and q_r =
+ * dmul_rn(y[r], y[r]), from the y[r] that was stored; dots[0] is the sum of
+ * the t_r and dots[1] the sum of the q_r over r < m, in rounded binary adds.
+ * The order of the adds is a function of the plan and of the path alone: it
+ * does not depend on the values, on what y or any plan-owned buffer held
+ * before, or on timing, and no floating-point atomic takes part in the
+ * reduction.  So the same plan with the same x and w gives the same 16 bytes
+ * on every call (COO: given its y).  The two paths need not agree bit for bit
+ * with each other, nor do different formats: a fused kernel's lane-to-row map
+ * differs between them (DIA holds row pairs, JDS is permuted, adaptive CSR is
+ * binned by length).  What is promised across all of them is
+ *   |dots[0] - sum_r w[r] y[r]| <= (m + 8) * 2^-53 * sum_r |w[r] y[r]|
+ * and likewise for dots[1] (one rounding per term, at most m - 1 adds in any
+ * order, 8 for the second-order terms).
+ * Rows >= m never contribute (padding, this header's opening comment): they
+ * are dropped by a select, never by a zero weight.  There is no shortcut for
+ * zeros: an empty row contributes w[r] * (+0.0), NaN where w[r] is not finite,
+ * and a plan with nothing stored (nnz = 0) gives y = +0.0 and computes the
+ * terms all the same.  m = 0 gives both dots as +0.0.  A non-finite term makes its dot
+ * non-finite, with the class an IEEE sum gives.  w may be x itself (m = n,
+ * CG's p . Ap); w and dots must not overlap y.  The buffer contract above
+ * holds: 8-byte alignment of x, y and w is enough, the alignment of w is
+ * independent of y's, and nothing outside [w, w + m) is read.
+ *
+ * Flags: SPMV_X_DEVICE, SPMV_Y_DEVICE, SPMV_X_STAGED and SPMV_ASYNC as for
+ * spmv_execute; SPMV_W_DEVICE, SPMV_DOTS_DEVICE: w, dots are device pointers
+ * on the plan's device (dots: 2 doubles, 8-byte aligned).  A host w is
+ * uploaded into a plan-owned staging vector of m doubles, allocated at the
+ * first use and counted in spmv_plan_info.device_bytes; host dots are copied
+ * back (16 bytes) after the stream is synchronised.  SPMV_ASYNC needs device
+ * x, y, w and dots.  Refusals come before any device work, all
+ * SPMV_ERROR_INVALID_VALUE: a NULL plan; a NULL x or y (with n, m > 0; x may
+ * be NULL with SPMV_X_STAGED); NULL dots; unknown flag bits; SPMV_Y_STAGED (y
+ * always travels back, there is nothing to fetch later); SPMV_ASYNC without all of SPMV_X_DEVICE, SPMV_Y_DEVICE and
+ * SPMV_DOTS_DEVICE (and SPMV_W_DEVICE when w is not NULL); SPMV_X_STAGED
+ * without a staged x.  The call clears the mark spmv_fetch_y needs, like any
+ * other non-staged execute.
+ *
+ * Paths (spmv_dot_path).  Every lane that stores a y[r] forms its terms, each
+ * wave reduces them with a fixed butterfly, the workgroup's waves are added in
+ * wave order, and one lane writes the pair with an ordinary store into the
+ * workgroup's own slot of a plan-owned partials array (2 doubles per
+ * workgroup of the plan's launch: plain device memory, allocated at the first
+ * use and counted in device_bytes; SPMV_ERROR_OUT_OF_MEMORY for it or for the
+ * w staging leaves the plan usable and y untouched).  Every workgroup writes
+ * its slot on every call.  A last launch of ONE workgroup adds the slots in a
+ * fixed order and writes dots.  Fused: the terms are formed in the store
+ * epilogue of the plan's own kernel, for one extra 8-byte read per row (w[r],
+ * loaded before the row is streamed, with the indexing the y store uses) --
+ * CSR (every kernel), ELL, DIA, and JDS without overflow rows.  Generic, every
+ * other plan (SS, COO, CSS, BIN, HYB, JDS with overflow rows, and any plan
+ * with nnz = 0 after its zero fill): the plan's own kernels write y, one pass
+ * streams y and w into the slots.
+ *
+ * Not covered: there is no dot form with alpha or beta, and none for
+ * spmv_execute_multi, HIP graphs, spmv_profile, spmv_dist_*, the drop-in
+ * (opt_hip.h) or the CSR5 handle. */
+#define SPMV_W_DEVICE    0x80u   /* w is a device pointer on the plan's device      */
+#define SPMV_DOTS_DEVICE 0x100u  /* dots is a device pointer (2 doubles, 8-byte aligned) */
+int spmv_execute_dot(spmv_plan_t plan, const double *x, double *y,
+                     const double *w, double *dots, uint32_t flags);
+
+/* iters back-to-back device-resident dot executes (device x, y, w or NULL, and
+ * dots) between two events on the plan's stream (the counterpart of spmv_time). */
+int spmv_time_dot(spmv_plan_t plan, const double *x_dev, double *y_dev,
+                  const double *w_dev, double *dots_dev, int32_t iters, double *ms);
+
+/* *fused = 1: the plan's kernel forms the terms in its store epilogue; 0:
+ * generic path.  A check and a documentation aid, like spmv_axpby_path. */
+int spmv_dot_path(spmv_plan_t plan, int32_t *fused);
 
 /* ---- value refresh: new values on a fixed sparsity pattern -----------------
  * Every layout decision of a plan (the format AUTO picks, slices, bins,

@@ -40,6 +40,7 @@ OPT_LIB_PATH = os.path.join(HERE, "libopt_hip.so")
 FORMATS = {"auto": 0, "csr": 1, "crs": 1, "ell": 2, "ss": 3, "dia": 4, "hyb": 5, "css": 6, "coo": 7, "jds": 8, "bin": 9}
 FORMAT_NAMES = {0: "auto", 1: "csr", 2: "ell", 3: "ss", 4: "dia", 5: "hyb", 6: "css", 7: "coo", 8: "jds", 9: "bin"}
 X_DEVICE, Y_DEVICE, ASYNC, X_STAGED, Y_STAGED = 0x1, 0x2, 0x4, 0x8, 0x10
+W_DEVICE, DOTS_DEVICE = 0x80, 0x100  # spmv_execute_dot
 CSR_DEVICE, VAL_DEVICE = 0x20, 0x40  # spmv_plan_update_prepare / spmv_plan_update_values
 GEN_UNIFORM, GEN_POWERLAW, GEN_BANDED = 1, 2, 3
 API_VERSION = 3  # SPMV_HIP_API_VERSION of the structs mirrored here
@@ -113,6 +114,7 @@ EXPORTS = [
     "spmv_execute_multi", "spmv_time_multi", "spmv_multi_path",
     "spmv_plan_update_prepare", "spmv_plan_update_values",
     "spmv_execute_axpby", "spmv_time_axpby", "spmv_axpby_path",
+    "spmv_execute_dot", "spmv_time_dot", "spmv_dot_path",
     "spmv_csr_transpose", "spmv_csr_transpose_device", "spmv_plan_create_csr_transposed",
     "spmv_plan_create_csr_device_transposed", "spmv_plan_is_transposed",
 ]
@@ -161,6 +163,9 @@ def lib():
     L.spmv_execute_axpby.argtypes = [vp, f64, vp, f64, vp, C.c_uint32]
     L.spmv_time_axpby.argtypes = [vp, f64, vp, f64, vp, i32, C.POINTER(f64)]
     L.spmv_axpby_path.argtypes = [vp, C.POINTER(i32)]
+    L.spmv_execute_dot.argtypes = [vp, vp, vp, vp, vp, C.c_uint32]
+    L.spmv_time_dot.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(f64)]
+    L.spmv_dot_path.argtypes = [vp, C.POINTER(i32)]
     L.spmv_plan_update_prepare.argtypes = [vp, vp, vp, C.c_uint32]
     L.spmv_plan_update_values.argtypes = [vp, vp, C.c_uint32]
     L.spmv_dist_fetch_y.argtypes = [vp, vp]
@@ -672,6 +677,54 @@ class Plan:
         (spmv_axpby_path)."""
         fused = C.c_int32()
         _check(lib().spmv_axpby_path(self._h, C.byref(fused)), "spmv_axpby_path")
+        return "fused" if fused.value else "generic"
+
+    def execute_dot(self, x, y, w=None, dots=None, async_: bool = False):
+        """y = A x, and from the same pass wy = sum w[r] * y[r] and yy = sum
+        y[r] * y[r] (spmv_execute_dot): no second read of y, no atomics, the
+        same 16 bytes on every call.  w: m doubles (numpy: host, staged into
+        the plan; torch CUDA: device; it may be x itself when m = n) or None:
+        wy = +0.0, nothing read.  dots None: returns (wy, yy) as floats, copied
+        back after the stream is synchronised; a float64 CUDA tensor of 2
+        entries: the dots are written there and nothing is returned (async_
+        needs device x, y, w and dots)."""
+        self._check_xy(x, y)
+        if w is not None:
+            _check_vec(w, self.m, "w", self.device, writable=False)
+        flags = (X_DEVICE if _is_device(x) else 0) | (Y_DEVICE if _is_device(y) else 0)
+        if _is_device(w):
+            flags |= W_DEVICE
+        if async_:
+            flags |= ASYNC
+        if dots is None:
+            out = (C.c_double * 2)()
+            _check(lib().spmv_execute_dot(self._h, _ptr(x), _ptr(y), _ptr(w), C.addressof(out), flags),
+                   "spmv_execute_dot")
+            return float(out[0]), float(out[1])
+        if not _is_device(dots) or dots.dtype != torch.float64 or dots.numel() != 2 or not dots.is_contiguous():
+            raise ValueError("dots must be a contiguous float64 CUDA tensor of 2 entries (or None)")
+        _check(lib().spmv_execute_dot(self._h, _ptr(x), _ptr(y), _ptr(w), _ptr(dots), flags | DOTS_DEVICE),
+               "spmv_execute_dot")
+        return None
+
+    def time_dot(self, x_dev, y_dev, w_dev, dots_dev, iters: int) -> float:
+        """Milliseconds for `iters` back-to-back dot executes (HIP events on
+        the plan's stream); device tensors throughout, w_dev may be None."""
+        self._check_xy(x_dev, y_dev)
+        if not (_is_device(x_dev) or self.n == 0) or not (_is_device(y_dev) or self.m == 0) or \
+                not (w_dev is None or _is_device(w_dev)) or not _is_device(dots_dev):
+            raise ValueError("time_dot() needs device tensors for x, y, w and dots")
+        ms = C.c_double()
+        _check(lib().spmv_time_dot(self._h, _ptr(x_dev), _ptr(y_dev), _ptr(w_dev), _ptr(dots_dev), iters,
+                                   C.byref(ms)), "spmv_time_dot")
+        return ms.value
+
+    def dot_path(self) -> str:
+        """"fused": the plan's kernel forms the dot terms in its store epilogue
+        (CSR, ELL, DIA, JDS without overflow rows); "generic": the plan's
+        kernels, then one pass over y and w (spmv_dot_path)."""
+        fused = C.c_int32()
+        _check(lib().spmv_dot_path(self._h, C.byref(fused)), "spmv_dot_path")
         return "fused" if fused.value else "generic"
 
     def _check_blocks(self, X, Y):

@@ -1,5 +1,6 @@
 // capi_execute.cpp -- the per-call side of include/spmv_hip.h: execute (one
-// vector, k vectors, alpha and beta), timing, graphs, the phase profile.
+// vector, k vectors, alpha and beta, with dot products), timing, graphs, the
+// phase profile.
 // Every entry point returns an int status.
 #include <algorithm>
 #include <new>
@@ -164,6 +165,103 @@ static int execute_impl(spmv_plan_t p, const Axpby &ab, const double *x, double 
     // opt_cusparse.cpp:82 -- D2H copy of y on every call
     if (y_host && p->m) SPMV_HIP_TRY(hipMemcpyAsync(y, dy, sizeof(double) * p->m, hipMemcpyDeviceToHost, p->stream));
     return finish_execute(p, flags, y_host);
+}
+
+// ---- y = A x with w . y and y . y (epilogues: k_csr / k_ell / k_dia.hip; second pass, finish: k_dot.hip) --
+
+// The workgroups of the plan's fused dot launch (0: it has none).  One writer
+// per row: CSR (every kernel), DIA, ELL and JDS without overflow rows; a plan
+// with nothing stored (nnz = 0) takes the generic path after its zero fill
+// (DESIGN §3.11).
+static int64_t dot_fused_blocks(const spmv_plan_s *p) {
+    if (p->nnz == 0) return 0;
+    switch (p->format) {
+        case SPMV_FORMAT_CSR: return csr_dot_blocks(p);
+        case SPMV_FORMAT_DIA: return dia_dot_blocks(p);
+        case SPMV_FORMAT_ELL: return ell_dot_blocks(p);
+        case SPMV_FORMAT_JDS: return jds_without_overflow(p) ? ell_dot_blocks(p) : 0;
+        default: return 0;
+    }
+}
+static bool dot_fused(const spmv_plan_s *p) { return dot_fused_blocks(p) > 0; }
+
+// the slots one dot execute writes: a function of the plan alone
+static int64_t dot_slots(const spmv_plan_s *p) {
+    const int64_t f = dot_fused_blocks(p);
+    return f > 0 ? f : dot_rows_blocks(p->m);
+}
+
+// the plan's partials, 2 doubles per slot, and behind them the 2 doubles a
+// host `dots` is copied from: plain hipMalloc memory, allocated at the first use
+static int dot_partials(spmv_plan_s *p) {
+    if (p->dot_part) return SPMV_SUCCESS;
+    void *q = nullptr;
+    SPMV_RETURN_IF(p->arena.alloc_plain(&q, sizeof(double) * (size_t)(2 * dot_slots(p) + 2)));
+    p->dot_part = (double *)q;
+    return SPMV_SUCCESS;
+}
+
+// the launches of one dot execute on device x, y, w (or null) and dots, on
+// p->stream: every slot is written by its workgroup, then one workgroup adds them
+static int dot_dispatch(spmv_plan_s *p, const double *x, double *y, const double *w, double *dots) {
+    const DotArgs d{w, p->dot_part};
+    if (dot_fused(p)) {
+        switch (p->format) {
+            case SPMV_FORMAT_CSR: SPMV_RETURN_IF(launch_csr(p, x, y, nullptr, &d)); break;
+            case SPMV_FORMAT_DIA: SPMV_RETURN_IF(launch_dia(p, x, y, nullptr, &d)); break;
+            default: SPMV_RETURN_IF(launch_ell(p, x, y, nullptr, &d));  // ELL, JDS without overflow rows
+        }
+    } else {
+        SPMV_RETURN_IF(dispatch(p, x, y));
+        SPMV_RETURN_IF(launch_dot_rows(p, y, w, p->dot_part));
+    }
+    return launch_dot_finish(p, p->dot_part, dot_slots(p), dots);
+}
+
+// The body of spmv_execute_dot (ms null) and spmv_time_dot (ms: device
+// buffers, `iters` dispatches between two events).
+static int dot_impl(spmv_plan_t p, const double *x, double *y, const double *w, double *dots, uint32_t flags,
+                    int32_t iters, double *ms) {
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    const bool timed = ms != nullptr;
+    const bool staged = (flags & SPMV_X_STAGED) != 0;
+    SPMV_CHECK_ARG((x != nullptr || p->n == 0 || staged) && (y != nullptr || p->m == 0), "x or y is NULL");
+    SPMV_CHECK_ARG(dots != nullptr, "spmv_execute_dot: dots is NULL");
+    SPMV_CHECK_ARG(!(flags & ~(SPMV_X_DEVICE | SPMV_Y_DEVICE | SPMV_ASYNC | SPMV_X_STAGED | SPMV_Y_STAGED |
+                               SPMV_W_DEVICE | SPMV_DOTS_DEVICE)),
+                   "spmv_execute_dot: unknown flag bits");
+    SPMV_CHECK_ARG(!(flags & SPMV_Y_STAGED), "spmv_execute_dot: SPMV_Y_STAGED is not supported");
+    const uint32_t all_dev = SPMV_X_DEVICE | SPMV_Y_DEVICE | SPMV_DOTS_DEVICE | (w ? SPMV_W_DEVICE : 0u);
+    SPMV_CHECK_ARG(!(flags & SPMV_ASYNC) || (flags & all_dev) == all_dev,
+                   "spmv_execute_dot: SPMV_ASYNC needs device x, y, w and dots");
+    SPMV_CHECK_ARG(!staged || p->x_stage != nullptr, "SPMV_X_STAGED without a previously staged x");
+    SPMV_CHECK_ARG(!timed || iters > 0, "spmv_time_dot: iters < 1");
+    SPMV_RETURN_IF(bind_device(p));
+    p->y_staged = false;  // like any other non-staged execute (spmv_fetch_y)
+    const bool x_host = !staged && !(flags & SPMV_X_DEVICE);
+    const bool y_dev = (flags & SPMV_Y_DEVICE) != 0;
+    const bool w_host = w != nullptr && !(flags & SPMV_W_DEVICE);
+    const bool dots_host = !(flags & SPMV_DOTS_DEVICE);
+    // every allocation comes first: out of memory leaves y untouched
+    if (x_host) SPMV_RETURN_IF(ensure_stage(p, &p->x_stage, p->n));
+    if (!y_dev) SPMV_RETURN_IF(ensure_stage(p, &p->y_stage, p->m));
+    if (w_host) SPMV_RETURN_IF(ensure_stage(p, &p->w_stage, p->m));
+    SPMV_RETURN_IF(dot_partials(p));
+    const double *dx = x_host || staged ? p->x_stage : x;
+    double *dy = y_dev ? y : p->y_stage;
+    const double *dw = w_host ? p->w_stage : w;
+    double *dd = dots_host ? p->dot_part + 2 * dot_slots(p) : dots;
+    if (timed) return time_on_stream(p->stream, iters, ms, [&] { return dot_dispatch(p, dx, dy, dw, dd); });
+    if (x_host && p->n) SPMV_HIP_TRY(hipMemcpyAsync(p->x_stage, x, sizeof(double) * p->n, hipMemcpyHostToDevice, p->stream));
+    if (w_host && p->m) SPMV_HIP_TRY(hipMemcpyAsync(p->w_stage, w, sizeof(double) * p->m, hipMemcpyHostToDevice, p->stream));
+    SPMV_RETURN_IF(dot_dispatch(p, dx, dy, dw, dd));
+    if (!y_dev && p->m) SPMV_HIP_TRY(hipMemcpyAsync(y, dy, sizeof(double) * p->m, hipMemcpyDeviceToHost, p->stream));
+    if (dots_host) {  // 16 bytes, once the stream has drained
+        SPMV_HIP_TRY(hipMemcpyAsync(dots, dd, 2 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+        SPMV_HIP_TRY(hipStreamSynchronize(p->stream));
+        return SPMV_SUCCESS;
+    }
+    return finish_execute(p, flags | (staged ? SPMV_X_DEVICE : 0u), !y_dev);
 }
 
 // Capture `reps` dispatches on a private stream (the plan's stream may be the
@@ -365,6 +463,25 @@ int spmv_axpby_path(spmv_plan_t p, int32_t *fused) {
     SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
     SPMV_CHECK_ARG(fused != nullptr, "fused out-pointer is NULL");
     *fused = axpby_fused(p) ? 1 : 0;
+    return SPMV_SUCCESS;
+}
+
+int spmv_execute_dot(spmv_plan_t p, const double *x, double *y, const double *w, double *dots, uint32_t flags) {
+    return dot_impl(p, x, y, w, dots, flags, 0, nullptr);
+}
+
+int spmv_time_dot(spmv_plan_t p, const double *x_dev, double *y_dev, const double *w_dev, double *dots_dev,
+                  int32_t iters, double *ms) {
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    SPMV_CHECK_ARG(ms != nullptr, "spmv_time_dot: ms is NULL");
+    return dot_impl(p, x_dev, y_dev, w_dev, dots_dev,
+                    SPMV_X_DEVICE | SPMV_Y_DEVICE | SPMV_W_DEVICE | SPMV_DOTS_DEVICE, iters, ms);
+}
+
+int spmv_dot_path(spmv_plan_t p, int32_t *fused) {
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    SPMV_CHECK_ARG(fused != nullptr, "fused out-pointer is NULL");
+    *fused = dot_fused(p) ? 1 : 0;
     return SPMV_SUCCESS;
 }
 

@@ -119,6 +119,54 @@ __device__ __forceinline__ double group_sum_dpp(double v) {
     return v;
 }
 
+// ---- spmv_execute_dot: the reduction every path shares ------
+
+// The terms of one stored row: t = w[r] * y[r] (have_w false: +0.0, w is
+// never read) and q = y[r] * y[r], rounded multiplies, added to the lane's
+// running pair.  `live` false (a row >= m, a lane without a row): the pair is
+// left as it is -- a select, never a zero weight.
+__device__ __forceinline__ void dot_add(double &t, double &q, bool live, bool have_w, double w, double y) {
+    const double t1 = __dadd_rn(t, __dmul_rn(w, y)), q1 = __dadd_rn(q, __dmul_rn(y, y));
+    t = live && have_w ? t1 : t;
+    q = live ? q1 : q;
+}
+
+// The workgroup's pair: every wave's lanes by the fixed butterfly
+// (group_sum_dpp<64>), then the waves in wave order through LDS.  EVERY
+// thread of the WAVES * 64-thread workgroup calls it (a barrier, and DPP reads
+// of neighbouring lanes); thread 0 returns with the sums.
+template <int WAVES>
+__device__ __forceinline__ void dot_block_sum(double &t, double &q) {
+    __shared__ double ws[WAVES][2];
+    t = group_sum_dpp<64>(t);
+    q = group_sum_dpp<64>(q);
+    if ((threadIdx.x & 63) == 0) {
+        ws[threadIdx.x >> 6][0] = t;
+        ws[threadIdx.x >> 6][1] = q;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        t = ws[0][0];
+        q = ws[0][1];
+#pragma unroll
+        for (int k = 1; k < WAVES; ++k) {
+            t = __dadd_rn(t, ws[k][0]);
+            q = __dadd_rn(q, ws[k][1]);
+        }
+    }
+}
+
+// ... and into the workgroup's own slot of the plan's partials: an ordinary
+// store pair from thread 0, on every call (a slot never carries an earlier
+// call's value).  No atomic, no counter.
+__device__ __forceinline__ void dot_block_store(double t, double q, double *__restrict__ part) {
+    dot_block_sum<4>(t, q);
+    if (threadIdx.x == 0) {
+        part[2 * (int64_t)blockIdx.x] = t;
+        part[2 * (int64_t)blockIdx.x + 1] = q;
+    }
+}
+
 // Inclusive prefix sum of an int across the 64-lane wave (Hillis-Steele).
 __device__ __forceinline__ int wave_inclusive_sum(int v, int lane) {
 #pragma unroll

@@ -475,6 +475,11 @@ struct spmv_plan_s {
     // spmv_execute_axpby, generic path: the row sums t = A x (m doubles, plain
     // hipMalloc: COO adds into it with f64 atomics), allocated at the first use
     double *ab_scratch = nullptr;
+    // spmv_execute_dot: the partials (2 doubles per workgroup of the plan's
+    // launch, then the 2 doubles a host `dots` is copied from; plain hipMalloc)
+    // and the staging of a host w (m doubles), each allocated at the first use
+    double *dot_part = nullptr;
+    double *w_stage = nullptr;
     int64_t stored_slots = 0;
     int64_t empty_rows = 0;
     int64_t algo_bytes = 0;
@@ -646,14 +651,36 @@ struct Axpby {
     double alpha, beta;
 };
 
+// spmv_execute_dot's fused launches: w (m doubles, or null: no w term) and the
+// plan's partials, one (t, q) slot per workgroup of the launch
+struct DotArgs {
+    const double *w;
+    double *part;
+};
+
 // kernels -- launch y = A x on p->stream (device x, y).  CSR, ELL (the sliced
 // ELL part of JDS included) and DIA take an optional Axpby: the same launch
-// with y = alpha * A x + beta * y in the store epilogue (one writer per row).
-int launch_csr(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab = nullptr);
-int launch_ell(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab = nullptr);
+// with y = alpha * A x + beta * y in the store epilogue (one writer per row),
+// or an optional DotArgs (never both): the same launch with the rows' terms
+// reduced into the partials.
+int launch_csr(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab = nullptr,
+               const DotArgs *dot = nullptr);
+int launch_ell(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab = nullptr,
+               const DotArgs *dot = nullptr);
+// workgroups of those launches (= slots written; 0: nothing to launch)
+int64_t csr_dot_blocks(const spmv_plan_s *p);
+int64_t ell_dot_blocks(const spmv_plan_s *p);
+int64_t dia_dot_blocks(const spmv_plan_s *p);
+// k_dot.hip -- the generic path's second pass over y and w (dot_rows_blocks(m)
+// slots) and the one-workgroup finish of either path: dots[0..1] = the slots'
+// sums in a fixed order (slots = 0: +0.0, +0.0)
+int64_t dot_rows_blocks(int64_t m);
+int launch_dot_rows(const spmv_plan_s *p, const double *y, const double *w, double *part);
+int launch_dot_finish(const spmv_plan_s *p, const double *part, int64_t slots, double *dots);
 int launch_hyb_overflow(const spmv_plan_s *p, const double *x, double *y);
 int launch_ss(const spmv_plan_s *p, const double *x, double *y);
-int launch_dia(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab = nullptr);
+int launch_dia(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab = nullptr,
+               const DotArgs *dot = nullptr);
 // k_axpby.hip -- y = alpha * t + beta * y over m rows on p->stream, the second
 // pass of the generic axpby path (t = nullptr: every t[r] is +0.0)
 int launch_axpby(const spmv_plan_s *p, double *y, const double *t, const Axpby &ab);

@@ -29,6 +29,11 @@
 // in the store epilogue, csr_slab_store<AB> / csr_store_row<ADD, AB>; the
 // row's writer loads its y0 before the row is streamed); alpha and beta are
 // arguments of the twins only.
+// Each also has a *_dot_kernel twin (spmv_execute_dot: the stored rows' terms
+// w[r] * y[r] and y[r]^2 reduced into the workgroup's slot of the plan's
+// partials, device.hpp dot_block_store; the writer loads its w[r] before the
+// row is streamed).  In a dot twin no wave or lane leaves early: one without
+// rows contributes +0.0 and still meets the reduction and its barrier.
 //
 // Algorithmic bytes per row: 12*nnz_i + rp bytes + 8 (y) and the
 // x gathers (8*n total, counted once).
@@ -261,6 +266,19 @@ __device__ __forceinline__ double csr_slab_y0(const double *__restrict__ y, int6
     return r0 + lane < m ? ld_stream(y + r0 + lane) : 0.0;
 }
 
+// lane t's w of the slab at r0 (spmv_execute_dot), indexed as the store; w
+// null: no w term, nothing read
+__device__ __forceinline__ double csr_slab_w(const double *__restrict__ w, int64_t r0, int64_t m) {
+    const int lane = threadIdx.x & 63;
+    return w != nullptr && r0 + lane < m ? w[r0 + lane] : 0.0;
+}
+// ... and its terms of the y[r0 + t] csr_slab_store just stored from ys
+__device__ __forceinline__ void csr_slab_dot(const double *ys, int64_t r0, int64_t m, bool have_w, double wr, double &t,
+                                             double &q) {
+    const int lane = threadIdx.x & 63;
+    dot_add(t, q, r0 + lane < m, have_w, wr, ys[lane]);
+}
+
 // csr_slab2<L, U, O32>: one wave per slab; each batch is loaded, gathered
 // from x in global memory and summed before the next one.
 template <int L, typename RP, int U, bool O32>
@@ -317,6 +335,41 @@ __global__ __launch_bounds__(256) void csr_slab2_axpby_kernel(int64_t m, const R
     csr_slab_store<true>(ysl[wv], y, r0, m, alpha, beta, y0);
 }
 
+// y = A x with the dot terms: csr_slab2's frame around the same batches (a
+// frame of its own, for csr_slab2_axpby_kernel's reason).  A wave past the
+// last slab runs no batch and stores nothing; its lanes' +0.0 meet the
+// workgroup's reduction like everyone's.
+template <int L, typename RP, int U, bool O32>
+__global__ __launch_bounds__(256) void csr_slab2_dot_kernel(int64_t m, const RP *__restrict__ rp,
+                                                            const int32_t *__restrict__ col,
+                                                            const double *__restrict__ val,
+                                                            const double *__restrict__ x, double *__restrict__ y,
+                                                            bool vh, const double *__restrict__ w,
+                                                            double *__restrict__ part) {
+    __shared__ double ysl[4][64];
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform (SGPR)
+    const int lane = threadIdx.x & 63;
+    const int64_t r0 = ((int64_t)blockIdx.x * 4 + wv) * 64;
+    double t = 0.0, q = 0.0;
+    if (r0 < m) {  // wave-uniform
+        const int64_t rl = r0 + lane;
+        const int64_t base = (int64_t)rp[r0] & ~(int64_t)3;
+        const int rpl = (int)((int64_t)rp[rl < m ? rl : m] - base);
+        const int rpe = (int)((int64_t)rp[r0 + 64 < m ? r0 + 64 : m] - base);
+        const double wr = csr_slab_w(w, r0, m);
+        const CsrStream<O32> A(col, val, base, vh);
+        auto xg = [&](int c) -> double { return *(const double *)at_bytes<O32>(x, c, 8); };
+        for (int st = 0; st < L; st += U) {
+            CsrBatch<L, U> B;
+            csr_batch_load(B, A, rpl, rpe, st);
+            csr_batch_sum(B, A, xg, ysl[wv], st);
+        }
+        csr_slab_store(ysl[wv], y, r0, m);
+        csr_slab_dot(ysl[wv], r0, m, w != nullptr, wr, t, q);
+    }
+    dot_block_store(t, q, part);
+}
+
 // csr_slabx<L, U, S, O32>: csr_slab2 for matrices whose rows stay near the
 // diagonal (banded, config 4).  A workgroup owns 256 S consecutive rows (each
 // wave S consecutive 64-row slabs) and reads x over one column window
@@ -329,12 +382,17 @@ __global__ __launch_bounds__(256) void csr_slab2_axpby_kernel(int64_t m, const R
 // issued before the window is staged.  Lanes whose loaded entry lies
 // outside the window (masked entries of a neighbouring row) read a clamped,
 // in-window slot.
-template <int L, typename RP, int U, int S, bool O32, bool AB = false>
+// DOT (spmv_execute_dot): a lane adds the terms of its S slabs' rows in slab
+// order as each slab is stored and the workgroup reduces once, after the last.
+template <int L, typename RP, int U, int S, bool O32, bool AB = false, bool DOT = false>
 __device__ __forceinline__ void csr_slabx_body(int64_t m, const RP *__restrict__ rp, const int32_t *__restrict__ col,
                                                const double *__restrict__ val, const double *__restrict__ x,
                                                double *__restrict__ y, const int32_t *__restrict__ win0, int32_t win,
                                                int64_t n, bool vh, double *xs, double (*ysl)[64],
-                                               double alpha = 0.0, double beta = 0.0) {
+                                               double alpha = 0.0, double beta = 0.0,
+                                               const double *__restrict__ w = nullptr,
+                                               double *__restrict__ part = nullptr) {
+    static_assert(!(AB && DOT), "the dot epilogue has no alpha and beta");
     constexpr int NB = L / U;   // batches per slab
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -355,6 +413,12 @@ __device__ __forceinline__ void csr_slabx_body(int64_t m, const RP *__restrict__
     for (int k = 0; k < S; ++k) {
         y0[k] = 0.0;
         if constexpr (AB) y0[k] = csr_slab_y0(y, r0 + 64 * k, m);
+    }
+    double wr[S], dt = 0.0, dq = 0.0;  // DOT: lane t's w of each slab, its running terms
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        wr[k] = 0.0;
+        if constexpr (DOT) wr[k] = csr_slab_w(w, r0 + 64 * k, m);
     }
     const CsrStream<O32> A(col, val, base, vh);
     auto load = [&](CsrBatch<L, U> &B, int i) {  // batch i: slab i / NB, steps (i % NB) U ..
@@ -382,6 +446,12 @@ __device__ __forceinline__ void csr_slabx_body(int64_t m, const RP *__restrict__
 #pragma unroll
             for (int k = 1; k < S; ++k) y0k = i / NB == k ? y0[k] : y0k;
             csr_slab_store<AB>(ysl[wv], y, r0 + 64 * (i / NB), m, alpha, beta, y0k);
+            if constexpr (DOT) {
+                double wk = wr[0];
+#pragma unroll
+                for (int k = 1; k < S; ++k) wk = i / NB == k ? wr[k] : wk;
+                csr_slab_dot(ysl[wv], r0 + 64 * (i / NB), m, w != nullptr, wk, dt, dq);
+            }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -414,6 +484,7 @@ __device__ __forceinline__ void csr_slabx_body(int64_t m, const RP *__restrict__
         if (i + 2 < nb) load(Ba, i + 2);
         compute(Bb, i + 1);
     }
+    if constexpr (DOT) dot_block_store(dt, dq, part);
 }
 
 template <int L, typename RP, int U, int S, bool O32>
@@ -441,6 +512,20 @@ __global__ __launch_bounds__(256) void csr_slabx_axpby_kernel(int64_t m, const R
     csr_slabx_body<L, RP, U, S, O32, true>(m, rp, col, val, x, y, win0, win, n, vh, xs, ysl, alpha, beta);
 }
 
+// y = A x with the dot terms: the same body with the dot epilogue
+template <int L, typename RP, int U, int S, bool O32>
+__global__ __launch_bounds__(256) void csr_slabx_dot_kernel(int64_t m, const RP *__restrict__ rp,
+                                                            const int32_t *__restrict__ col,
+                                                            const double *__restrict__ val,
+                                                            const double *__restrict__ x, double *__restrict__ y,
+                                                            const int32_t *__restrict__ win0, int32_t win, int64_t n,
+                                                            bool vh, const double *__restrict__ w,
+                                                            double *__restrict__ part) {
+    extern __shared__ double xs[];  // [win]
+    __shared__ double ysl[4][64];
+    csr_slabx_body<L, RP, U, S, O32, false, true>(m, rp, col, val, x, y, win0, win, n, vh, xs, ysl, 0.0, 0.0, w, part);
+}
+
 // Adaptive CSR in ONE launch: workgroup ranges map to the length bins
 // (blk_off), so all bins run concurrently instead of back to back; the bin
 // test is workgroup-uniform (no divergence).  Bin b has L = kCsrBinLanes[b]
@@ -453,31 +538,46 @@ struct CsrBinTable {
 // the short-row bins fill in behind them instead of forming the tail
 constexpr int kCsrLaunchOrder[kCsrBins] = {7, 6, 5, 4, 3, 2, 1, 0};
 
-template <int L, typename RP, bool ADD, bool AB>
+// DOT (spmv_execute_dot): the row's writer adds its terms to (dt, dq); a
+// group past the bin's last row walks an empty row and stores nothing instead
+// of leaving (the workgroup reduces after the bins' switch).
+template <int L, typename RP, bool ADD, bool AB, bool DOT>
 __device__ __forceinline__ void csr_rows_body(int64_t wg, int64_t nrows, const int32_t *__restrict__ rows,
                                               const RP *__restrict__ rp, const int32_t *__restrict__ col,
                                               const double *__restrict__ val, const double *__restrict__ x,
                                               double *__restrict__ y, const int32_t *__restrict__ yrow, double alpha,
-                                              double beta) {
+                                              double beta, const double *__restrict__ w, double &dt, double &dq) {
     const int64_t g = (wg * 256 + threadIdx.x) / L;
     const int lane = threadIdx.x & (L - 1);
-    if (g >= nrows) return;
-    const int64_t row = rows[g];
+    if constexpr (!DOT) {
+        if (g >= nrows) return;
+    }
+    const bool live = !DOT || g < nrows;
+    const int64_t row = live ? (int64_t)rows[g] : 0;
     double y0 = 0.0;  // AB: the writer's y[row], loaded before the row's walk
     if constexpr (AB) {
         if (lane == 0) y0 = ld_stream(y + row);
     }
-    const double acc = group_sum<L>(csr_row_sum<L>(rp[row], rp[row + 1], lane, col, val, x, false));
-    if (lane == 0) csr_store_row<ADD, AB>(y, yrow, row, acc, alpha, beta, y0);
+    double wr = 0.0;  // DOT: the writer's w[row], likewise
+    if constexpr (DOT) {
+        if (w != nullptr && live && lane == 0) wr = w[row];
+    }
+    const auto s = live ? rp[row] : (RP)0, e = live ? rp[row + 1] : (RP)0;
+    const double acc = group_sum<L>(csr_row_sum<L>(s, e, lane, col, val, x, false));
+    if (lane == 0 && live) csr_store_row<ADD, AB>(y, yrow, row, acc, alpha, beta, y0);
+    if constexpr (DOT) dot_add(dt, dq, lane == 0 && live, w != nullptr, wr, acc);
 }
 
-template <typename RP, bool ADD, bool AB>
+template <typename RP, bool ADD, bool AB, bool DOT = false>
 __device__ __forceinline__ void csr_adaptive_body(const CsrBinTable &t, const int32_t *__restrict__ rows,
                                                   const RP *__restrict__ rp, const int32_t *__restrict__ col,
                                                   const double *__restrict__ val, const double *__restrict__ x,
                                                   double *__restrict__ y, const int32_t *__restrict__ yrow,
-                                                  double alpha, double beta) {
+                                                  double alpha, double beta, const double *__restrict__ w = nullptr,
+                                                  double *__restrict__ dpart = nullptr) {
+    static_assert(!DOT || (!ADD && !AB), "the dot epilogue has no add and no alpha and beta");
     __shared__ double part[4];
+    double dt = 0.0, dq = 0.0;  // DOT: this thread's terms
     const int64_t blk = blockIdx.x;
     int k = 0;
     while (k < kCsrBins - 1 && blk >= t.blk_off[k + 1]) ++k;  // uniform
@@ -486,13 +586,13 @@ __device__ __forceinline__ void csr_adaptive_body(const CsrBinTable &t, const in
     const int32_t *br = rows + t.row_off[b];
     const int64_t n = t.row_off[b + 1] - t.row_off[b];
     switch (b) {
-        case 0: csr_rows_body<1, RP, ADD, AB>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta); break;
-        case 1: csr_rows_body<2, RP, ADD, AB>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta); break;
-        case 2: csr_rows_body<4, RP, ADD, AB>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta); break;
-        case 3: csr_rows_body<8, RP, ADD, AB>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta); break;
-        case 4: csr_rows_body<16, RP, ADD, AB>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta); break;
-        case 5: csr_rows_body<32, RP, ADD, AB>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta); break;
-        case 6: csr_rows_body<64, RP, ADD, AB>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta); break;
+        case 0: csr_rows_body<1, RP, ADD, AB, DOT>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta, w, dt, dq); break;
+        case 1: csr_rows_body<2, RP, ADD, AB, DOT>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta, w, dt, dq); break;
+        case 2: csr_rows_body<4, RP, ADD, AB, DOT>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta, w, dt, dq); break;
+        case 3: csr_rows_body<8, RP, ADD, AB, DOT>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta, w, dt, dq); break;
+        case 4: csr_rows_body<16, RP, ADD, AB, DOT>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta, w, dt, dq); break;
+        case 5: csr_rows_body<32, RP, ADD, AB, DOT>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta, w, dt, dq); break;
+        case 6: csr_rows_body<64, RP, ADD, AB, DOT>(wg, n, br, rp, col, val, x, y, yrow, alpha, beta, w, dt, dq); break;
         default: {
             // one workgroup per row: four wave sums added in wave order
             const int64_t row = br[wg];
@@ -500,16 +600,25 @@ __device__ __forceinline__ void csr_adaptive_body(const CsrBinTable &t, const in
             if constexpr (AB) {
                 if (threadIdx.x == 0) y0 = ld_stream(y + row);
             }
+            double wr = 0.0;
+            if constexpr (DOT) {
+                if (w != nullptr && threadIdx.x == 0) wr = w[row];
+            }
             const double acc =
                 group_sum<64>(csr_row_sum<256>(rp[row], rp[row + 1], (int)threadIdx.x, col, val, x, false));
             if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
             __syncthreads();
-            if (threadIdx.x == 0)
+            if constexpr (DOT) {  // thread 0 holds the row's term
+                const double sum = __dadd_rn(__dadd_rn(part[0], part[1]), __dadd_rn(part[2], part[3]));
+                if (threadIdx.x == 0) csr_store_row<ADD, AB>(y, yrow, row, sum, alpha, beta, y0);
+                dot_add(dt, dq, threadIdx.x == 0, w != nullptr, wr, sum);
+            } else if (threadIdx.x == 0)
                 csr_store_row<ADD, AB>(y, yrow, row,
                                        __dadd_rn(__dadd_rn(part[0], part[1]), __dadd_rn(part[2], part[3])), alpha,
                                        beta, y0);
         }
     }
+    if constexpr (DOT) dot_block_store(dt, dq, dpart);
 }
 
 template <typename RP, bool ADD>
@@ -533,11 +642,20 @@ __global__ __launch_bounds__(256) void csr_adaptive_axpby_kernel(CsrBinTable t, 
     csr_adaptive_body<RP, false, true>(t, rows, rp, col, val, x, y, nullptr, alpha, beta);
 }
 
-// one launch of the adaptive kernel over length bins (bin_off: host offsets)
-template <typename RP, bool ADD>
-static int launch_adaptive(const spmv_plan_s *p, const int64_t *bin_off, const int32_t *bin_rows, const RP *rp,
-                           const int32_t *col, const double *val, const double *x, double *y,
-                           const int32_t *yrow, const Axpby *ab = nullptr) {
+// y = A x with the dot terms: the same body with the dot epilogue
+template <typename RP>
+__global__ __launch_bounds__(256) void csr_adaptive_dot_kernel(CsrBinTable t, const int32_t *__restrict__ rows,
+                                                               const RP *__restrict__ rp,
+                                                               const int32_t *__restrict__ col,
+                                                               const double *__restrict__ val,
+                                                               const double *__restrict__ x, double *__restrict__ y,
+                                                               const double *__restrict__ w,
+                                                               double *__restrict__ part) {
+    csr_adaptive_body<RP, false, false, true>(t, rows, rp, col, val, x, y, nullptr, 0.0, 0.0, w, part);
+}
+
+// the bins' workgroup ranges, in launch order (bin_off: host offsets)
+static CsrBinTable csr_bin_table(const int64_t *bin_off) {
     CsrBinTable t;
     t.blk_off[0] = 0;
     for (int b = 0; b <= kCsrBins; ++b) t.row_off[b] = bin_off[b];
@@ -547,8 +665,23 @@ static int launch_adaptive(const spmv_plan_s *p, const int64_t *bin_off, const i
         const int L = kCsrBinLanes[b];
         t.blk_off[k + 1] = t.blk_off[k] + (L >= 256 ? n : (n * L + 255) / 256);
     }
+    return t;
+}
+
+// one launch of the adaptive kernel over length bins
+template <typename RP, bool ADD>
+static int launch_adaptive(const spmv_plan_s *p, const int64_t *bin_off, const int32_t *bin_rows, const RP *rp,
+                           const int32_t *col, const double *val, const double *x, double *y,
+                           const int32_t *yrow, const Axpby *ab = nullptr, const DotArgs *dot = nullptr) {
+    const CsrBinTable t = csr_bin_table(bin_off);
     if (t.blk_off[kCsrBins] == 0) return SPMV_SUCCESS;
     if constexpr (!ADD) {
+        if (dot) {
+            hipLaunchKernelGGL((csr_adaptive_dot_kernel<RP>), dim3((unsigned)t.blk_off[kCsrBins]), dim3(256), 0,
+                               p->stream, t, bin_rows, rp, col, val, x, y, dot->w, dot->part);
+            SPMV_HIP_TRY(hipGetLastError());
+            return SPMV_SUCCESS;
+        }
         if (ab) {
             hipLaunchKernelGGL((csr_adaptive_axpby_kernel<RP>), dim3((unsigned)t.blk_off[kCsrBins]), dim3(256), 0,
                                p->stream, t, bin_rows, rp, col, val, x, y, ab->alpha, ab->beta);
@@ -573,7 +706,7 @@ static int launch_adaptive(const spmv_plan_s *p, const int64_t *bin_off, const i
 constexpr int kCsrBatchSteps = 4;  // slab: steps whose loads are issued together
 
 template <int L, typename RP>
-static void launch_slab(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab) {
+static void launch_slab(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab, const DotArgs *dot) {
     constexpr int UU = kCsrBatchSteps < L ? kCsrBatchSteps : L;
     constexpr int S = kCsrSlabsPerWave;  // granules (64-row slabs per wave) per workgroup
     const int64_t waves = (p->m + 63) / 64;
@@ -587,6 +720,11 @@ static void launch_slab(const spmv_plan_s *p, const double *x, double *y, const 
         };
         // 32-bit offsets span the wave's S slabs (off32 is per single slab)
         const bool o32 = c.off32 && (S == 1 || (int64_t)S * c.slab_max + 512 < ((int64_t)1 << 28));
+        if (dot) {
+            if (o32) go(csr_slabx_dot_kernel<L, RP, UU, S, true>, dot->w, dot->part);
+            else go(csr_slabx_dot_kernel<L, RP, UU, S, false>, dot->w, dot->part);
+            return;
+        }
         if (ab) {
             if (o32) go(csr_slabx_axpby_kernel<L, RP, UU, S, true>, ab->alpha, ab->beta);
             else go(csr_slabx_axpby_kernel<L, RP, UU, S, false>, ab->alpha, ab->beta);
@@ -601,6 +739,11 @@ static void launch_slab(const spmv_plan_s *p, const double *x, double *y, const 
         hipLaunchKernelGGL(kern, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, p->stream, p->m,
                            (const RP *)c.row_ptr, c.col, c.val, x, y, c.val_halves, ab_args...);
     };
+    if (dot) {
+        if (c.off32) go(csr_slab2_dot_kernel<L, RP, UU, true>, dot->w, dot->part);
+        else go(csr_slab2_dot_kernel<L, RP, UU, false>, dot->w, dot->part);
+        return;
+    }
     if (ab) {
         if (c.off32) go(csr_slab2_axpby_kernel<L, RP, UU, true>, ab->alpha, ab->beta);
         else go(csr_slab2_axpby_kernel<L, RP, UU, false>, ab->alpha, ab->beta);
@@ -612,44 +755,55 @@ static void launch_slab(const spmv_plan_s *p, const double *x, double *y, const 
 }
 
 template <int L, typename RP>
-static int launch_csr_t(const spmv_plan_s *p, int64_t nrows, const double *x, double *y, const Axpby *ab) {
+static int launch_csr_t(const spmv_plan_s *p, int64_t nrows, const double *x, double *y, const Axpby *ab,
+                       const DotArgs *dot) {
     if (nrows == 0) return SPMV_SUCCESS;
-    launch_slab<L, RP>(p, x, y, ab);
+    launch_slab<L, RP>(p, x, y, ab, dot);
     SPMV_HIP_TRY(hipGetLastError());
     return SPMV_SUCCESS;
 }
 
 template <typename RP>
 static int launch_csr_lanes(const spmv_plan_s *p, int lanes, int64_t nrows, const double *x, double *y,
-                            const Axpby *ab) {
+                            const Axpby *ab, const DotArgs *dot) {
     switch (lanes) {
-        case 1: return launch_csr_t<1, RP>(p, nrows, x, y, ab);
-        case 2: return launch_csr_t<2, RP>(p, nrows, x, y, ab);
-        case 4: return launch_csr_t<4, RP>(p, nrows, x, y, ab);
-        case 8: return launch_csr_t<8, RP>(p, nrows, x, y, ab);
-        case 16: return launch_csr_t<16, RP>(p, nrows, x, y, ab);
-        case 32: return launch_csr_t<32, RP>(p, nrows, x, y, ab);
-        case 64: return launch_csr_t<64, RP>(p, nrows, x, y, ab);
+        case 1: return launch_csr_t<1, RP>(p, nrows, x, y, ab, dot);
+        case 2: return launch_csr_t<2, RP>(p, nrows, x, y, ab, dot);
+        case 4: return launch_csr_t<4, RP>(p, nrows, x, y, ab, dot);
+        case 8: return launch_csr_t<8, RP>(p, nrows, x, y, ab, dot);
+        case 16: return launch_csr_t<16, RP>(p, nrows, x, y, ab, dot);
+        case 32: return launch_csr_t<32, RP>(p, nrows, x, y, ab, dot);
+        case 64: return launch_csr_t<64, RP>(p, nrows, x, y, ab, dot);
         default: set_error("csr lanes must be a power of two in [1,64]"); return SPMV_ERROR_INVALID_VALUE;
     }
 }
 
 template <typename RP>
-static int launch_csr_rp(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab) {
+static int launch_csr_rp(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab, const DotArgs *dot) {
     const CsrDev &c = p->csr;
-    if (!c.bin_rows) return launch_csr_lanes<RP>(p, c.lanes, p->m, x, y, ab);
+    if (!c.bin_rows) return launch_csr_lanes<RP>(p, c.lanes, p->m, x, y, ab, dot);
     // adaptive: every bin in one launch (workgroup ranges per bin)
     return launch_adaptive<RP, false>(p, c.bin_off, c.bin_rows, (const RP *)c.row_ptr, c.col, c.val, x, y, nullptr,
-                                      ab);
+                                      ab, dot);
 }
 
-int launch_csr(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab) {
+// the workgroups of the plan's dot launch: the slots it writes (0: nothing
+// stored, no launch)
+int64_t csr_dot_blocks(const spmv_plan_s *p) {
+    const CsrDev &c = p->csr;
+    if (p->nnz == 0 || p->m == 0) return 0;
+    if (c.bin_rows) return csr_bin_table(c.bin_off).blk_off[kCsrBins];
+    if (c.win0) return (p->m + 256 * kCsrSlabsPerWave - 1) / (256 * kCsrSlabsPerWave);
+    return ((p->m + 63) / 64 + 3) / 4;
+}
+
+int launch_csr(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab, const DotArgs *dot) {
     if (p->nnz == 0) {  // no entries: y = 0 without touching x (x may be NULL when n == 0)
         if (p->m && ab) return launch_axpby(p, y, nullptr, *ab);  // alpha * (+0.0) + beta * y
         if (p->m) SPMV_HIP_TRY(hipMemsetAsync(y, 0, sizeof(double) * (size_t)p->m, p->stream));
         return SPMV_SUCCESS;
     }
-    return p->csr.rp64 ? launch_csr_rp<int64_t>(p, x, y, ab) : launch_csr_rp<int32_t>(p, x, y, ab);
+    return p->csr.rp64 ? launch_csr_rp<int64_t>(p, x, y, ab, dot) : launch_csr_rp<int32_t>(p, x, y, ab, dot);
 }
 
 // HYB / JDS overflow: the adaptive kernel over the overflow rows binned by

@@ -53,13 +53,23 @@ namespace spmv {
 // (device.hpp axpby).  y0 is read with the very access the store uses -- the
 // 16-byte row pair where y is 16-byte aligned, else two scalars -- and its
 // load is issued before the diagonal loop, so it never trails the wave.
-template <int K, int UNROLL, bool LDSX, int YMODE, bool AB = false>
+//
+// DOT (K = 1, spmv_execute_dot): the lane's terms of the two sums it stores,
+// added in row order, go into the workgroup's slot of `part` (device.hpp
+// dot_block_store).  w[r], w[r + 1] are 8-byte loads (w's alignment is its
+// own, YMODE describes y's), issued where y0's are.  No lane leaves early: one
+// whose rows are >= m walks no diagonal, stores nothing, and still meets the
+// reduction and its barrier.
+template <int K, int UNROLL, bool LDSX, int YMODE, bool AB = false, bool DOT = false>
 __device__ __forceinline__ void dia_body(int64_t m, int64_t mp, int64_t n, int n_diags,
                                          const int32_t *__restrict__ off, int32_t off_min, int32_t win, int32_t wpad,
                                          const double *__restrict__ val, const double *__restrict__ X, int64_t ldx,
                                          double *__restrict__ Y, int64_t ldy, int32_t group, double *xs,
-                                         double alpha = 0.0, double beta = 0.0) {
+                                         double alpha = 0.0, double beta = 0.0,
+                                         const double *__restrict__ w = nullptr,
+                                         double *__restrict__ part = nullptr) {
     static_assert(!AB || K == 1, "the axpby epilogue is single-vector");
+    static_assert(!DOT || (K == 1 && !AB), "the dot epilogue is single-vector, without alpha and beta");
     const int64_t r0 = 2 * (int64_t)blockIdx.x * blockDim.x;
     const int64_t r = r0 + 2 * threadIdx.x;
     // group > 0 (DiaDev::group): blocks interleaved per group of `group`
@@ -83,7 +93,10 @@ __device__ __forceinline__ void dia_body(int64_t m, int64_t mp, int64_t n, int n
         }
         __syncthreads();
     }
-    if (r >= m) return;
+    if constexpr (!DOT) {
+        if (r >= m) return;
+    }
+    const int nd = DOT && r >= m ? 0 : n_diags;  // the diagonals this lane walks
     f64x2 y0 = {0.0, 0.0};
     if constexpr (AB) {  // the store's own branches, below
         if (r + 1 < m && (reinterpret_cast<uintptr_t>(Y) & 15) == 0) {
@@ -92,6 +105,11 @@ __device__ __forceinline__ void dia_body(int64_t m, int64_t mp, int64_t n, int n
             y0.x = ld_stream(Y + r);
             if (r + 1 < m) y0.y = ld_stream(Y + r + 1);
         }
+    }
+    f64x2 wr = {0.0, 0.0};
+    if constexpr (DOT) {
+        if (w != nullptr && r < m) wr.x = w[r];
+        if (w != nullptr && r + 1 < m) wr.y = w[r + 1];
     }
     double a0[K], a1[K];
 #pragma unroll
@@ -124,7 +142,7 @@ __device__ __forceinline__ void dia_body(int64_t m, int64_t mp, int64_t n, int n
         }
     };
     int d = 0;
-    for (; d + UNROLL <= n_diags; d += UNROLL) {
+    for (; d + UNROLL <= nd; d += UNROLL) {
         f64x2 v[UNROLL];
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u) v[u] = ld_stream2(vb + (int64_t)(d + u) * dstride);
@@ -145,7 +163,7 @@ __device__ __forceinline__ void dia_body(int64_t m, int64_t mp, int64_t n, int n
             for (int u = 0; u < UNROLL; ++u) step(v[u], off[d + u]);
         }
     }
-    for (; d < n_diags; ++d) step(ld_stream2(vb + (int64_t)d * dstride), off[d]);
+    for (; d < nd; ++d) step(ld_stream2(vb + (int64_t)d * dstride), off[d]);
     if constexpr (K == 1) {
         if constexpr (AB) {
             a0[0] = axpby(alpha, a0[0], beta, y0.x);
@@ -153,7 +171,9 @@ __device__ __forceinline__ void dia_body(int64_t m, int64_t mp, int64_t n, int n
         }
         // y is written once and not re-read: the row pair as one 16-byte
         // nontemporal store where y is 16-byte aligned (r is even)
-        if (r + 1 < m && (reinterpret_cast<uintptr_t>(Y) & 15) == 0) {
+        if (DOT && r >= m) {
+            // no row: nothing to store
+        } else if (r + 1 < m && (reinterpret_cast<uintptr_t>(Y) & 15) == 0) {
             f64x2 yv;
             yv.x = a0[0];
             yv.y = a1[0];
@@ -163,6 +183,12 @@ __device__ __forceinline__ void dia_body(int64_t m, int64_t mp, int64_t n, int n
         } else {
             Y[r] = a0[0];
             if (r + 1 < m) Y[r + 1] = a1[0];
+        }
+        if constexpr (DOT) {
+            double t = 0.0, q = 0.0;
+            dot_add(t, q, r < m, w != nullptr, wr.x, a0[0]);
+            dot_add(t, q, r + 1 < m, w != nullptr, wr.y, a1[0]);
+            dot_block_store(t, q, part);
         }
     } else {
         st_row<K>(Y + r * ldy, a0);
@@ -191,6 +217,18 @@ __global__ __launch_bounds__(256) void dia_axpby_kernel(int64_t m, int64_t mp, i
                                                         double beta) {
     extern __shared__ double xs[];
     dia_body<1, 8, LDSX, 0, true>(m, mp, n, n_diags, off, off_min, win, 0, val, x, 1, y, 1, group, xs, alpha, beta);
+}
+
+// y = A x with the rows' dot terms reduced into the plan's partials
+template <bool LDSX>
+__global__ __launch_bounds__(256) void dia_dot_kernel(int64_t m, int64_t mp, int64_t n, int n_diags,
+                                                      const int32_t *__restrict__ off, int32_t off_min, int32_t win,
+                                                      const double *__restrict__ val, const double *__restrict__ x,
+                                                      double *__restrict__ y, int32_t group,
+                                                      const double *__restrict__ w, double *__restrict__ part) {
+    extern __shared__ double xs[];
+    dia_body<1, 8, LDSX, 0, false, true>(m, mp, n, n_diags, off, off_min, win, 0, val, x, 1, y, 1, group, xs, 0.0, 0.0,
+                                         w, part);
 }
 
 template <int K, bool LDSX>
@@ -222,7 +260,12 @@ static DiaGeom dia_geom(const spmv_plan_s *p) {
     return {dim3((unsigned)(((p->m + 1) / 2 + 255) / 256)), off_min, 512 + (int64_t)off_max - off_min + 1};
 }
 
-int launch_dia(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab) {
+// the launch's workgroups: the slots a dot launch writes (0: no stored diagonal)
+int64_t dia_dot_blocks(const spmv_plan_s *p) {
+    return p->m > 0 && p->dia.n_diags > 0 ? (int64_t)dia_geom(p).blocks.x : 0;
+}
+
+int launch_dia(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab, const DotArgs *dot) {
     const DiaDev &d = p->dia;
     if (p->m == 0) return SPMV_SUCCESS;
     if (d.n_diags == 0) {  // no stored diagonal: y = 0 (axpby: alpha * (+0.0) + beta * y)
@@ -253,6 +296,12 @@ int launch_dia(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab
         hipLaunchKernelGGL(kernel, g.blocks, dim3(256), lds, p->stream, p->m, d.mp, p->n, d.n_diags, d.off, g.off_min,
                            ldsx ? (int32_t)g.win : 0, d.val, x, y, d.group, ab_args...);
     };
+    if (dot) {  // the product's shape with the dot epilogue
+        if (fits && !(dbg & 1)) go(dia_dot_kernel<true>, true, dot->w, dot->part);
+        else go(dia_dot_kernel<false>, false, dot->w, dot->part);
+        SPMV_HIP_TRY(hipGetLastError());
+        return SPMV_SUCCESS;
+    }
     if (ab) {  // the product's shape (8 diagonals in flight, nontemporal y) with the axpby epilogue
         if (fits && !(dbg & 1)) go(dia_axpby_kernel<true>, true, ab->alpha, ab->beta);
         else go(dia_axpby_kernel<false>, false, ab->alpha, ab->beta);

@@ -43,17 +43,29 @@ __device__ __forceinline__ const char *ell_at(const void *base, int64_t byte_off
 // AB (K = 1, spmv_execute_axpby): the store writes alpha * sum + beta * y0
 // (device.hpp axpby); y0 = Y[row], through perm for JDS, is loaded before the
 // slots like the perm entry itself.
-template <int K, int UNROLL, bool PERM, bool O32, bool AB = false>
+//
+// DOT (K = 1, spmv_execute_dot): the lane's terms w[row] * y[row] and y[row]^2
+// of the sum it stores (w through perm for JDS, loaded where y0 is) go into
+// the workgroup's slot of `part` (device.hpp dot_block_store): no wave leaves
+// early -- a slice past the last one has no slots and no rows, and still meets
+// the reduction and its barrier.
+template <int K, int UNROLL, bool PERM, bool O32, bool AB = false, bool DOT = false>
 __device__ __forceinline__ void ell_slice_body(int64_t m, int64_t n_slices, const int32_t *__restrict__ perm,
                                                const int64_t *__restrict__ slice_off,
                                                const int32_t *__restrict__ col, const double *__restrict__ val,
                                                const double *__restrict__ X, int64_t ldx, double *__restrict__ Y,
-                                               int64_t ldy, double alpha = 0.0, double beta = 0.0) {
+                                               int64_t ldy, double alpha = 0.0, double beta = 0.0,
+                                               const double *__restrict__ w = nullptr,
+                                               double *__restrict__ part = nullptr) {
     static_assert(!AB || K == 1, "the axpby epilogue is single-vector");
+    static_assert(!DOT || (K == 1 && !AB), "the dot epilogue is single-vector, without alpha and beta");
     const int64_t slice = (int64_t)blockIdx.x * (blockDim.x / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    if (slice >= n_slices) return;
-    const int64_t srow = slice * 64 + lane;
+    if constexpr (!DOT) {
+        if (slice >= n_slices) return;
+    }
+    const bool dead = DOT && slice >= n_slices;  // wave-uniform
+    const int64_t srow = dead ? m : slice * 64 + lane;
     // JDS: the matrix row, loaded before the slots so its latency hides
     // behind them instead of trailing the wave
     const int64_t row = PERM ? (srow < m ? (int64_t)perm[srow] : 0) : srow;
@@ -61,8 +73,12 @@ __device__ __forceinline__ void ell_slice_body(int64_t m, int64_t n_slices, cons
     if constexpr (AB) {
         if (srow < m) y0 = ld_stream(Y + row * ldy);
     }
-    const int64_t base = slice_off[slice];
-    const int64_t quads = (slice_off[slice + 1] - base) >> 8;  // (width/4)
+    double wr = 0.0;
+    if constexpr (DOT) {
+        if (w != nullptr && srow < m) wr = w[row];
+    }
+    const int64_t base = slice_off[dead ? 0 : slice];
+    const int64_t quads = dead ? 0 : (slice_off[slice + 1] - base) >> 8;  // (width/4)
     const int32_t *cs = col + base;  // wave-uniform slice bases
     const double *vs = val + base;
     auto ldc = [&](int64_t q) { return ld_stream4((const int32_t *)ell_at<O32>(cs, (q * 256 + lane * 4) * 4)); };
@@ -123,6 +139,11 @@ __device__ __forceinline__ void ell_slice_body(int64_t m, int64_t n_slices, cons
     }
     if constexpr (AB) acc[0] = axpby(alpha, acc[0], beta, y0);
     if (srow < m) st_row<K>(Y + row * ldy, acc);
+    if constexpr (DOT) {
+        double t = 0.0, q = 0.0;
+        dot_add(t, q, srow < m, w != nullptr, wr, acc[0]);
+        dot_block_store(t, q, part);
+    }
 }
 
 // the single vector: K = 1, the unit strides fold away
@@ -147,6 +168,19 @@ __global__ __launch_bounds__(256) void ell_slice_axpby_kernel(int64_t m, int64_t
                                                               const double *__restrict__ x, double *__restrict__ y,
                                                               double alpha, double beta) {
     ell_slice_body<1, UNROLL, PERM, O32, true>(m, n_slices, perm, slice_off, col, val, x, 1, y, 1, alpha, beta);
+}
+
+// y = A x with the rows' dot terms reduced into the plan's partials
+template <int UNROLL, bool PERM, bool O32>
+__global__ __launch_bounds__(256) void ell_slice_dot_kernel(int64_t m, int64_t n_slices,
+                                                            const int32_t *__restrict__ perm,
+                                                            const int64_t *__restrict__ slice_off,
+                                                            const int32_t *__restrict__ col,
+                                                            const double *__restrict__ val,
+                                                            const double *__restrict__ x, double *__restrict__ y,
+                                                            const double *__restrict__ w, double *__restrict__ part) {
+    ell_slice_body<1, UNROLL, PERM, O32, false, true>(m, n_slices, perm, slice_off, col, val, x, 1, y, 1, 0.0, 0.0, w,
+                                                      part);
 }
 
 template <int K, int UNROLL, bool PERM, bool O32>
@@ -181,13 +215,16 @@ static bool ell_o32(const spmv_plan_s *p, int64_t ldx) {
 // with the axpby epilogue)
 template <int K, int U>
 static void launch_ell_ku(const spmv_plan_s *p, const double *X, int64_t ldx, double *Y, int64_t ldy, size_t lds,
-                          bool o32, const Axpby *ab = nullptr) {
+                          bool o32, const Axpby *ab = nullptr, const DotArgs *dot = nullptr) {
     const EllDev &e = p->ell;
     const dim3 blocks((unsigned)((e.n_slices + 3) / 4));
     auto go = [&](auto perm, auto o) {
         constexpr bool P = decltype(perm)::value, O = decltype(o)::value;
         if constexpr (K == 1) {
-            if (ab)
+            if (dot)
+                hipLaunchKernelGGL((ell_slice_dot_kernel<U, P, O>), blocks, dim3(256), lds, p->stream, p->m,
+                                   e.n_slices, e.perm, e.slice_off, e.col, e.val, X, Y, dot->w, dot->part);
+            else if (ab)
                 hipLaunchKernelGGL((ell_slice_axpby_kernel<U, P, O>), blocks, dim3(256), lds, p->stream, p->m,
                                    e.n_slices, e.perm, e.slice_off, e.col, e.val, X, Y, ab->alpha, ab->beta);
             else
@@ -205,12 +242,15 @@ static void launch_ell_ku(const spmv_plan_s *p, const double *X, int64_t ldx, do
     else go_o(std::false_type{});
 }
 
-int launch_ell(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab) {
+// the launch's workgroups (4 slices each): the slots a dot launch writes
+int64_t ell_dot_blocks(const spmv_plan_s *p) { return (p->ell.n_slices + 3) / 4; }
+
+int launch_ell(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab, const DotArgs *dot) {
     const EllDev &e = p->ell;
     if (e.n_slices == 0) return SPMV_SUCCESS;
     // 2 quads (4 slots each) per lane per iteration: 2 beat 4 by 28 % at
     // config 4, 5 % at config 2 (round 4 A/B)
-    launch_ell_ku<1, 2>(p, x, 1, y, 1, ell_lds(e), ell_o32(p, 1), ab);
+    launch_ell_ku<1, 2>(p, x, 1, y, 1, ell_lds(e), ell_o32(p, 1), ab, dot);
     SPMV_HIP_TRY(hipGetLastError());
     return SPMV_SUCCESS;
 }
