@@ -84,7 +84,8 @@ extern "C" {
  * points (spmv_plan_update_prepare, spmv_plan_update_values) and the BLAS form
  * (spmv_execute_axpby, spmv_time_axpby, spmv_axpby_path) and the execute
  * with dot products (spmv_execute_dot, spmv_time_dot, spmv_dot_path, with the
- * flags SPMV_W_DEVICE and SPMV_DOTS_DEVICE).  Callers may
+ * flags SPMV_W_DEVICE and SPMV_DOTS_DEVICE) and the solver (spmv_cg_solve,
+ * spmv_cg_path, the flags SPMV_CG_DEVICE and SPMV_CG_GRAPH).  Callers may
  * check spmv_api_version() == SPMV_HIP_API_VERSION once at startup; the
  * structs are only ever filled by spmv_options_default / spmv_plan_info of a
  * library with the same version. */
@@ -631,6 +632,96 @@ int spmv_time_dot(spmv_plan_t plan, const double *x_dev, double *y_dev,
 /* *fused = 1: the plan's kernel forms the terms in its store epilogue; 0:
  * generic path.  A check and a documentation aid, like spmv_axpby_path. */
 int spmv_dot_path(spmv_plan_t plan, int32_t *fused);
+
+/* ---- conjugate gradients on a plan: solve A x = b, scalars on the device ---
+ * spmv_cg_solve runs Hestenes-Stiefel conjugate gradients for a symmetric
+ * positive definite A held by a square plan.  x is the initial guess on entry
+ * and the iterate on exit; dinv is NULL or m doubles of a diagonal
+ * preconditioner already inverted (Jacobi: 1 / a_ii -- the plan keeps no CSR,
+ * so the caller supplies it).  The solve stops when rr <= rtol * rtol * bb
+ * (rr = r . r of the recurrence, bb = b . b), tested before the first
+ * iteration too, or after max_iters iterations.  The function returns
+ * synchronised.
+ *
+ * The iteration.  Every operation is a rounded multiply, add or divide, never
+ * an FMA.  Init: r = b; r = (-1) * A x + 1 * r through the plan's own
+ * spmv_execute_axpby launches; z = dinv (.) r (no dinv: z = r), p = z, and rz
+ * = r . z, rr, bb.  Per iteration:
+ *   q = A p, pq = p . q    the plan's own spmv_execute_dot launches with x = w
+ *                          = p: q has the bits spmv_execute gives on p, pq
+ *                          the bits of spmv_execute_dot's dots[0]
+ *   alpha = rz / pq;  x = x + alpha * p;  r = r - alpha * q;  z = dinv (.) r
+ *   rz_new = r . z, rr = r . r;  beta = rz_new / rz;  p = z + beta * p
+ * alpha, beta, rz, rr, pq, the iteration counter and the status live in a
+ * plan-owned block of device memory: the kernels read them there, one lane
+ * writes them with ordinary stores, and the host copies the block back once
+ * per check_every (>= 1) iterations.  max_iters is enforced on the device, so
+ * it need not be a multiple of check_every: once the solve is done the
+ * launches left in a check interval return at once and move nothing in x, r,
+ * p or the counter (the SpMV among them still runs, into the workspace q; the
+ * host cuts the last interval at max_iters so that none runs past it).  The dot products are reduced as spmv_execute_dot's (lanes,
+ * waves and workgroups in a fixed order, a function of m alone); no
+ * floating-point atomic takes part, except the y-atomics COO plans already
+ * have.  So x and info are a function of the plan, b, the x of entry, dinv,
+ * rtol and max_iters: not of check_every, of SPMV_CG_GRAPH, of host or device
+ * buffers, or of timing.
+ *
+ * Breakdown: if pq is not a finite number > 0 (an indefinite A, non-finite
+ * data) no row of x, r or p moves in that iteration, the counter stays and
+ * the status is SPMV_CG_BREAKDOWN.  Symmetry of A is the caller's
+ * responsibility.
+ *
+ * Flags.  SPMV_CG_DEVICE: b, x and dinv are device pointers on the plan's
+ * device (all or none; 8-byte alignment is enough, the buffer contract
+ * above holds and nothing outside [v, v + m) is read or written); without it
+ * they are host pointers, staged into plan-owned vectors.  SPMV_CG_GRAPH: one
+ * check interval (check_every iterations, a linear chain) is captured once
+ * into a HIP graph and launched per interval (a last interval cut at
+ * max_iters is launched kernel by kernel); the graph is cached on the plan,
+ * rebuilt when x's or dinv's device address or check_every changes (rtol and
+ * max_iters travel through the scalar block) and destroyed with the plan.  No
+ * device pointer moves on spmv_plan_update_values: a cached graph replays the
+ * refreshed values.  CSS plans return SPMV_ERROR_NOT_SUPPORTED with the flag,
+ * as spmv_graph_create does.
+ *
+ * Memory: r, p, q (3 m doubles), the partials (4 doubles per workgroup), the
+ * scalar block and, for host pointers, the staging of b, x and dinv, besides
+ * what the plan's axpby and dot executes own.  Plain device memory, allocated
+ * at the first solve before any device work, counted in
+ * spmv_plan_info.device_bytes, freed with the plan; SPMV_ERROR_OUT_OF_MEMORY
+ * leaves the plan usable and x untouched.
+ *
+ * Refusals, all SPMV_ERROR_INVALID_VALUE before any device work, x untouched:
+ * a NULL plan; NULL info; NULL b or x with m > 0; m != n; unknown flag bits
+ * (every SPMV_X_* / SPMV_Y_* / SPMV_ASYNC bit included); max_iters < 0;
+ * check_every < 1; rtol < 0 or NaN.  m = 0 gives SPMV_CG_CONVERGED with 0
+ * iterations; max_iters = 0 runs the init only (CONVERGED or MAX_ITERS).  The
+ * call clears the mark spmv_fetch_y needs, like any other non-staged execute.
+ *
+ * Not covered: other Krylov methods, non-symmetric A (an indefinite A ends in
+ * SPMV_CG_BREAKDOWN), spmv_dist_*, the drop-in (opt_hip.h), the CSR5 handle, a
+ * multi-vector or block form, spmv_profile phases. */
+#define SPMV_CG_DEVICE 0x200u  /* b, x and dinv are device pointers on the plan's device (all or none) */
+#define SPMV_CG_GRAPH  0x400u  /* replay each check interval as one hipGraph launch */
+
+enum { SPMV_CG_CONVERGED = 0, SPMV_CG_MAX_ITERS = 1, SPMV_CG_BREAKDOWN = 2 };
+
+typedef struct spmv_cg_info {
+    int32_t status;      /* SPMV_CG_*                                        */
+    int32_t iterations;  /* completed iterations (x updates applied)         */
+    double rr, bb;       /* r.r of the recurrence at exit, b.b               */
+    double rz;           /* r.z at exit (= rr without dinv)                  */
+    double pq;           /* the last p.Ap the SpMV produced (+0.0 if none)   */
+} spmv_cg_info_t;
+
+int spmv_cg_solve(spmv_plan_t plan, const double *b, double *x, const double *dinv,
+                  double rtol, int32_t max_iters, int32_t check_every,
+                  uint32_t flags, spmv_cg_info_t *info);
+
+/* *launches_per_iteration: the kernel launches one iteration enqueues (5 on a
+ * plan whose dot path is fused: SpMV, dot finish, update, finish, direction).
+ * A documentation aid, like spmv_dot_path. */
+int spmv_cg_path(spmv_plan_t plan, int32_t *launches_per_iteration);
 
 /* ---- value refresh: new values on a fixed sparsity pattern -----------------
  * Every layout decision of a plan (the format AUTO picks, slices, bins,

@@ -41,6 +41,8 @@ FORMATS = {"auto": 0, "csr": 1, "crs": 1, "ell": 2, "ss": 3, "dia": 4, "hyb": 5,
 FORMAT_NAMES = {0: "auto", 1: "csr", 2: "ell", 3: "ss", 4: "dia", 5: "hyb", 6: "css", 7: "coo", 8: "jds", 9: "bin"}
 X_DEVICE, Y_DEVICE, ASYNC, X_STAGED, Y_STAGED = 0x1, 0x2, 0x4, 0x8, 0x10
 W_DEVICE, DOTS_DEVICE = 0x80, 0x100  # spmv_execute_dot
+CG_DEVICE, CG_GRAPH = 0x200, 0x400  # spmv_cg_solve
+CG_STATUS = {0: "converged", 1: "max_iters", 2: "breakdown"}  # SPMV_CG_*
 CSR_DEVICE, VAL_DEVICE = 0x20, 0x40  # spmv_plan_update_prepare / spmv_plan_update_values
 GEN_UNIFORM, GEN_POWERLAW, GEN_BANDED = 1, 2, 3
 API_VERSION = 3  # SPMV_HIP_API_VERSION of the structs mirrored here
@@ -91,6 +93,12 @@ class PlanInfo(C.Structure):
         return d
 
 
+class CgInfo(C.Structure):
+    """spmv_cg_info_t."""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("rr", C.c_double), ("bb", C.c_double),
+                ("rz", C.c_double), ("pq", C.c_double)]
+
+
 class GenSpec(C.Structure):
     _fields_ = [("kind", C.c_int32), ("per_row", C.c_int32), ("m", C.c_int64), ("n", C.c_int64),
                 ("max_len", C.c_int32), ("alpha", C.c_double), ("band_lo", C.c_int32),
@@ -115,6 +123,7 @@ EXPORTS = [
     "spmv_plan_update_prepare", "spmv_plan_update_values",
     "spmv_execute_axpby", "spmv_time_axpby", "spmv_axpby_path",
     "spmv_execute_dot", "spmv_time_dot", "spmv_dot_path",
+    "spmv_cg_solve", "spmv_cg_path",
     "spmv_csr_transpose", "spmv_csr_transpose_device", "spmv_plan_create_csr_transposed",
     "spmv_plan_create_csr_device_transposed", "spmv_plan_is_transposed",
 ]
@@ -166,6 +175,8 @@ def lib():
     L.spmv_execute_dot.argtypes = [vp, vp, vp, vp, vp, C.c_uint32]
     L.spmv_time_dot.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(f64)]
     L.spmv_dot_path.argtypes = [vp, C.POINTER(i32)]
+    L.spmv_cg_solve.argtypes = [vp, vp, vp, vp, f64, i32, i32, C.c_uint32, C.POINTER(CgInfo)]
+    L.spmv_cg_path.argtypes = [vp, C.POINTER(i32)]
     L.spmv_plan_update_prepare.argtypes = [vp, vp, vp, C.c_uint32]
     L.spmv_plan_update_values.argtypes = [vp, vp, C.c_uint32]
     L.spmv_dist_fetch_y.argtypes = [vp, vp]
@@ -726,6 +737,38 @@ class Plan:
         fused = C.c_int32()
         _check(lib().spmv_dot_path(self._h, C.byref(fused)), "spmv_dot_path")
         return "fused" if fused.value else "generic"
+
+    def cg(self, b, x, dinv=None, rtol: float = 1e-8, max_iters: int = 1000, check_every: int = 8,
+           graph: bool = False) -> dict:
+        """Solve A x = b by conjugate gradients on the device (spmv_cg_solve):
+        x is the initial guess on entry and the iterate on exit, dinv None or
+        the inverted diagonal (Jacobi).  The scalars stay in device memory; the
+        host looks at them once per `check_every` iterations.  graph=True
+        replays each check interval as one HIP graph, cached on the plan.
+        numpy arrays are host buffers, torch CUDA tensors device buffers (all
+        or none).  Returns status ("converged", "max_iters", "breakdown"),
+        iterations, rr, bb, rz and pq; the same plan, b, x, dinv, rtol and
+        max_iters give the same bytes whatever check_every and graph are."""
+        vecs = [("b", b, False), ("x", x, True)] + ([("dinv", dinv, False)] if dinv is not None else [])
+        for name, v, writable in vecs:
+            _check_vec(v, self.m, name, self.device, writable=writable)
+        on_device = {_is_device(v) for _, v, _ in vecs if v is not None}
+        if len(on_device) > 1:
+            raise ValueError("cg(): b, x and dinv must all be numpy arrays (host) or all torch CUDA tensors (device)")
+        flags = (CG_DEVICE if on_device == {True} else 0) | (CG_GRAPH if graph else 0)
+        info = CgInfo()
+        _check(lib().spmv_cg_solve(self._h, _ptr(b), _ptr(x), _ptr(dinv), float(rtol), int(max_iters),
+                                   int(check_every), flags, C.byref(info)), "spmv_cg_solve")
+        out = {k: getattr(info, k) for k, _ in CgInfo._fields_}
+        out["status"] = CG_STATUS.get(info.status, str(info.status))
+        return out
+
+    def cg_path(self) -> int:
+        """Kernel launches per iteration of cg() (spmv_cg_path): 5 where
+        dot_path() is "fused"."""
+        n = C.c_int32()
+        _check(lib().spmv_cg_path(self._h, C.byref(n)), "spmv_cg_path")
+        return n.value
 
     def _check_blocks(self, X, Y):
         k, ldx = _check_block(X, self.n, "X", self.device, writable=False)

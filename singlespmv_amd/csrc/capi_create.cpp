@@ -548,6 +548,7 @@ int spmv_plan_create_coo(int32_t m, int32_t n, int32_t nnz, const int32_t *row_i
 int spmv_plan_destroy(spmv_plan_t p) {
     if (!p) return SPMV_SUCCESS;
     (void)bind_device(p);
+    cg_graph_release(p);
     p->arena.release();
     delete p;
     return SPMV_SUCCESS;

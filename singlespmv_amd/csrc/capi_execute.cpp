@@ -1,6 +1,6 @@
 // capi_execute.cpp -- the per-call side of include/spmv_hip.h: execute (one
-// vector, k vectors, alpha and beta, with dot products), timing, graphs, the
-// phase profile.
+// vector, k vectors, alpha and beta, with dot products), the conjugate-gradient
+// solver, timing, graphs, the phase profile.
 // Every entry point returns an int status.
 #include <algorithm>
 #include <new>
@@ -296,6 +296,170 @@ static int graph_capture(spmv_plan_s *p, const double *x, double *y, int32_t rep
     return SPMV_SUCCESS;
 }
 
+// ---- conjugate gradients on a plan (vector kernels: k_cg.hip) --
+
+// one plain allocation of the solver's, at the first use
+template <typename T>
+static int cg_alloc(spmv_plan_s *p, T **buf, size_t bytes) {
+    if (*buf) return SPMV_SUCCESS;
+    void *q = nullptr;
+    SPMV_RETURN_IF(p->arena.alloc_plain(&q, bytes));
+    *buf = (T *)q;
+    return SPMV_SUCCESS;
+}
+
+// Everything a solve allocates, before any device work: r, p, q, the partials
+// (two arrays of 2 doubles per workgroup: the init pass fills both), the
+// scalar block, the staging of host vectors, and what the plan's own axpby and
+// dot executes need.
+static int cg_workspace(spmv_plan_s *p, bool host, bool have_dinv) {
+    CgWork &w = p->cg;
+    const size_t vec = sizeof(double) * (size_t)p->m;
+    SPMV_RETURN_IF(cg_alloc(p, &w.r, vec));
+    SPMV_RETURN_IF(cg_alloc(p, &w.p, vec));
+    SPMV_RETURN_IF(cg_alloc(p, &w.q, vec));
+    SPMV_RETURN_IF(cg_alloc(p, &w.part, sizeof(double) * (size_t)(4 * cg_blocks(p->m))));
+    SPMV_RETURN_IF(cg_alloc(p, &w.state, sizeof(CgState)));
+    if (host) {
+        SPMV_RETURN_IF(cg_alloc(p, &w.b_stage, vec));
+        SPMV_RETURN_IF(cg_alloc(p, &w.x_stage, vec));
+        if (have_dinv) SPMV_RETURN_IF(cg_alloc(p, &w.dinv_stage, vec));
+    }
+    SPMV_RETURN_IF(axpby_scratch(p, 1.0));
+    return dot_partials(p);
+}
+
+// the launches of one iteration on p->stream: q = A p and p . q by the plan's
+// own dot execute (w = x = p, the dots into the scalar block), then the update,
+// the one-workgroup finish and the new direction
+static int cg_iteration(spmv_plan_s *p, double *x, const double *dinv) {
+    const CgWork &w = p->cg;
+    SPMV_RETURN_IF(dot_dispatch(p, w.p, w.q, w.p, w.state->dots));
+    SPMV_RETURN_IF(launch_cg_update(p, x, dinv));
+    SPMV_RETURN_IF(launch_cg_finish(p));
+    return launch_cg_direction(p, dinv);
+}
+
+void cg_graph_release(spmv_plan_s *p) {
+    CgWork &w = p->cg;
+    if (w.exec) (void)hipGraphExecDestroy(w.exec);
+    if (w.graph) (void)hipGraphDestroy(w.graph);
+    w.exec = nullptr;
+    w.graph = nullptr;
+}
+
+// The graph of one check interval: `every` iterations, a linear chain,
+// captured on a private stream as graph_capture does and instantiated once.
+// rtol and max_iters travel through the scalar block, b is read by the init
+// pass only: the key is what the captured launches hold, (x, dinv, every).
+static int cg_graph(spmv_plan_s *p, double *x, const double *dinv, int32_t every) {
+    CgWork &w = p->cg;
+    if (w.exec && w.key_x == x && w.key_dinv == dinv && w.key_every == every) return SPMV_SUCCESS;
+    cg_graph_release(p);
+    hipStream_t cs = nullptr;
+    SPMV_HIP_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+    const hipStream_t saved = p->stream;
+    const int saved_prof = p->prof_k;
+    p->stream = cs;
+    p->prof_k = -1;
+    int st = SPMV_SUCCESS;
+    hipGraph_t g = nullptr;
+    hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+    if (e == hipSuccess) {
+        for (int32_t k = 0; k < every && st == SPMV_SUCCESS; ++k) st = cg_iteration(p, x, dinv);
+        e = hipStreamEndCapture(cs, &g);
+    }
+    p->stream = saved;
+    p->prof_k = saved_prof;
+    (void)hipStreamDestroy(cs);
+    hipGraphExec_t ex = nullptr;
+    if (st == SPMV_SUCCESS && e == hipSuccess) e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+    if (st != SPMV_SUCCESS || e != hipSuccess) {
+        if (g) (void)hipGraphDestroy(g);
+        if (st != SPMV_SUCCESS) return st;
+        set_error(std::string("spmv_cg_solve: graph of a check interval: ") + hipGetErrorString(e));
+        (void)hipGetLastError();
+        return SPMV_ERROR_HIP;
+    }
+    w.graph = g;
+    w.exec = ex;
+    w.key_x = x;
+    w.key_dinv = dinv;
+    w.key_every = every;
+    return SPMV_SUCCESS;
+}
+
+static int cg_solve(spmv_plan_t p, const double *b, double *x, const double *dinv, double rtol, int32_t max_iters,
+                    int32_t check_every, uint32_t flags, spmv_cg_info_t *info) {
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    SPMV_CHECK_ARG(info != nullptr, "spmv_cg_solve: info is NULL");
+    SPMV_CHECK_ARG((b != nullptr && x != nullptr) || p->m == 0, "spmv_cg_solve: b or x is NULL");
+    SPMV_CHECK_ARG(p->m == p->n, "spmv_cg_solve: the plan is not square");
+    SPMV_CHECK_ARG(!(flags & ~(SPMV_CG_DEVICE | SPMV_CG_GRAPH)), "spmv_cg_solve: unknown flag bits");
+    SPMV_CHECK_ARG(max_iters >= 0, "spmv_cg_solve: max_iters < 0");
+    SPMV_CHECK_ARG(check_every >= 1, "spmv_cg_solve: check_every < 1");
+    SPMV_CHECK_ARG(rtol >= 0.0, "spmv_cg_solve: rtol is negative or NaN");
+    if ((flags & SPMV_CG_GRAPH) && p->format == SPMV_FORMAT_CSS) {
+        // as spmv_graph_create: the sweep's per-launch sequence number is a kernel argument
+        set_error("spmv_cg_solve: CSS plans cannot be replayed from a graph (SPMV_CG_GRAPH)");
+        return SPMV_ERROR_NOT_SUPPORTED;
+    }
+    p->y_staged = false;  // like any other non-staged execute (spmv_fetch_y)
+    CgState h = {};
+    if (p->m > 0) {
+        SPMV_RETURN_IF(bind_device(p));
+        const bool host = !(flags & SPMV_CG_DEVICE);
+        if (!host) {
+            const void *ptrs[3] = {b, x, dinv};
+            SPMV_RETURN_IF(check_device_arrays(ptrs, dinv ? 3 : 2, p->device, "spmv_cg_solve",
+                                               ": SPMV_CG_DEVICE needs device memory on the plan's device"));
+        }
+        // every allocation comes first: out of memory leaves x untouched
+        SPMV_RETURN_IF(cg_workspace(p, host, dinv != nullptr));
+        CgWork &w = p->cg;
+        const size_t vec = sizeof(double) * (size_t)p->m;
+        double *dx = x;
+        const double *db = b, *dd = dinv;
+        if (host) {
+            SPMV_HIP_TRY(hipMemcpyAsync(w.b_stage, b, vec, hipMemcpyHostToDevice, p->stream));
+            SPMV_HIP_TRY(hipMemcpyAsync(w.x_stage, x, vec, hipMemcpyHostToDevice, p->stream));
+            if (dinv) SPMV_HIP_TRY(hipMemcpyAsync(w.dinv_stage, dinv, vec, hipMemcpyHostToDevice, p->stream));
+            db = w.b_stage;
+            dx = w.x_stage;
+            dd = dinv ? w.dinv_stage : nullptr;
+        }
+        if (flags & SPMV_CG_GRAPH) SPMV_RETURN_IF(cg_graph(p, dx, dd, check_every));
+        // r = b - A x through the plan's own axpby, then z, p and the first scalars
+        SPMV_HIP_TRY(hipMemcpyAsync(w.r, db, vec, hipMemcpyDeviceToDevice, p->stream));
+        SPMV_RETURN_IF(axpby_dispatch(p, Axpby{-1.0, 1.0}, dx, w.r));
+        SPMV_RETURN_IF(launch_cg_init(p, db, dd, rtol * rtol, max_iters));
+        for (;;) {  // max_iters is enforced on the device: the loop ends on done
+            SPMV_HIP_TRY(hipMemcpyAsync(&h, w.state, sizeof(h), hipMemcpyDeviceToHost, p->stream));
+            SPMV_HIP_TRY(hipStreamSynchronize(p->stream));
+            if (h.done) break;
+            // the last interval is cut at max_iters (launches past it would only
+            // run the SpMV for nothing): plain launches, the graph holds check_every
+            const int32_t left = std::max<int32_t>(1, max_iters - h.iterations);
+            if ((flags & SPMV_CG_GRAPH) && left >= check_every) {
+                SPMV_HIP_TRY(hipGraphLaunch(w.exec, p->stream));
+            } else {
+                for (int32_t k = 0; k < std::min(check_every, left); ++k) SPMV_RETURN_IF(cg_iteration(p, dx, dd));
+            }
+        }
+        if (host) {
+            SPMV_HIP_TRY(hipMemcpyAsync(x, w.x_stage, vec, hipMemcpyDeviceToHost, p->stream));
+            SPMV_HIP_TRY(hipStreamSynchronize(p->stream));
+        }
+    }
+    info->status = h.status;  // m = 0: CONVERGED, nothing ran
+    info->iterations = h.iterations;
+    info->rr = h.rr;
+    info->bb = h.bb;
+    info->rz = h.rz;
+    info->pq = h.pq;
+    return SPMV_SUCCESS;
+}
+
 // ---- multi-vector execute (Y = A X, k interleaved right-hand sides) ---------
 
 // Widths with a fused kernel (k_dia.hip, k_ell.hip), per format, widest first.
@@ -482,6 +646,20 @@ int spmv_dot_path(spmv_plan_t p, int32_t *fused) {
     SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
     SPMV_CHECK_ARG(fused != nullptr, "fused out-pointer is NULL");
     *fused = dot_fused(p) ? 1 : 0;
+    return SPMV_SUCCESS;
+}
+
+int spmv_cg_solve(spmv_plan_t p, const double *b, double *x, const double *dinv, double rtol, int32_t max_iters,
+                  int32_t check_every, uint32_t flags, spmv_cg_info_t *info) {
+    return cg_solve(p, b, x, dinv, rtol, max_iters, check_every, flags, info);
+}
+
+int spmv_cg_path(spmv_plan_t p, int32_t *launches_per_iteration) {
+    SPMV_CHECK_ARG(p != nullptr, "plan is NULL");
+    SPMV_CHECK_ARG(launches_per_iteration != nullptr, "launches out-pointer is NULL");
+    // the plan's dot execute (fused: its kernel and the dot finish; generic: its
+    // kernels, the pass over q and the dot finish), then update, finish, direction
+    *launches_per_iteration = (dot_fused(p) ? 2 : p->n_kernels + 2) + 3;
     return SPMV_SUCCESS;
 }
 

@@ -167,6 +167,36 @@ __device__ __forceinline__ void dot_block_store(double t, double q, double *__re
     }
 }
 
+// The one-workgroup finish of a partials array (dot_finish_kernel, and the
+// solver's cg_*finish_kernel): thread i of kDotFinishThreads takes slots i,
+// i + 1024, ... ascending, four 16-byte loads in flight and their adds in slot
+// order; then the butterfly, then the waves in wave order.  Thread 0 returns
+// with the sums; slots = 0: +0.0, +0.0.  Every thread calls it.
+constexpr int kDotFinishThreads = 1024;
+__device__ __forceinline__ void dot_slots_sum(const double *__restrict__ part, int64_t slots, double &t, double &q) {
+    constexpr int64_t T = kDotFinishThreads;
+    const f64x2 *ps = reinterpret_cast<const f64x2 *>(part);
+    t = 0.0;
+    q = 0.0;
+    int64_t i = threadIdx.x;
+    for (; i + 3 * T < slots; i += 4 * T) {
+        f64x2 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = ps[i + u * T];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            t = __dadd_rn(t, v[u].x);
+            q = __dadd_rn(q, v[u].y);
+        }
+    }
+    for (; i < slots; i += T) {
+        const f64x2 v = ps[i];
+        t = __dadd_rn(t, v.x);
+        q = __dadd_rn(q, v.y);
+    }
+    dot_block_sum<kDotFinishThreads / 64>(t, q);
+}
+
 // Inclusive prefix sum of an int across the 64-lane wave (Hillis-Steele).
 __device__ __forceinline__ int wave_inclusive_sum(int v, int lane) {
 #pragma unroll

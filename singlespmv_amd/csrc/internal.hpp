@@ -440,6 +440,32 @@ struct UpdState {
     double *stage = nullptr;  // host val staging, nnz doubles (first host update)
 };
 
+// spmv_cg_solve: the solver's scalars, device-resident between two host looks
+// (k_cg.hip writes them, one lane, ordinary stores; the host copies the block
+// back once per check interval).  dots is where the plan's dot finish writes
+// p . Ap (and Ap . Ap) of the current iteration.
+struct CgState {
+    double dots[2];
+    double rz, rr, bb;   // r . z, r . r of the recurrence, b . b
+    double pq;           // the p . Ap of the latest iteration that was not skipped (+0.0: none)
+    double beta;         // rz_new / rz of that iteration
+    double rtol2;        // rtol * rtol
+    int32_t done, status, iterations, max_iters;
+};
+// the solver's workspace on a plan: everything plain hipMalloc memory,
+// allocated at the first solve (host staging at the first host solve)
+struct CgWork {
+    double *r = nullptr, *p = nullptr, *q = nullptr;  // m doubles each, 16-byte aligned
+    double *part = nullptr;   // [2][2 * slots]: (r . z, r . r) per workgroup; init: then (-, b . b)
+    CgState *state = nullptr;
+    double *b_stage = nullptr, *x_stage = nullptr, *dinv_stage = nullptr;  // host b, x, dinv
+    // SPMV_CG_GRAPH: one check interval, instantiated; rebuilt when the key changes
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    const double *key_x = nullptr, *key_dinv = nullptr;
+    int32_t key_every = 0;
+};
+
 }  // namespace spmv
 
 struct spmv_plan_s {
@@ -480,6 +506,7 @@ struct spmv_plan_s {
     // and the staging of a host w (m doubles), each allocated at the first use
     double *dot_part = nullptr;
     double *w_stage = nullptr;
+    spmv::CgWork cg;  // spmv_cg_solve
     int64_t stored_slots = 0;
     int64_t empty_rows = 0;
     int64_t algo_bytes = 0;
@@ -677,6 +704,20 @@ int64_t dia_dot_blocks(const spmv_plan_s *p);
 int64_t dot_rows_blocks(int64_t m);
 int launch_dot_rows(const spmv_plan_s *p, const double *y, const double *w, double *part);
 int launch_dot_finish(const spmv_plan_s *p, const double *part, int64_t slots, double *dots);
+// k_cg.hip -- the vector kernels of spmv_cg_solve on p->stream.
+// cg_blocks(m) workgroups each, a function of m alone (= slots of cg.part);
+// dinv null: z = r.  Every kernel but the init pair returns at once when
+// state->done is set.
+int64_t cg_blocks(int64_t m);
+// z = dinv (.) r, p = z, the slots' (r . z, r . r) and (-, b . b); then one
+// workgroup: rz, rr, bb, the whole state, done for rr <= rtol2 * bb or max_iters = 0
+int launch_cg_init(const spmv_plan_s *p, const double *b, const double *dinv, double rtol2, int32_t max_iters);
+// alpha = rz / pq; x += alpha p; r -= alpha q; the slots' (r . z, r . r)
+int launch_cg_update(const spmv_plan_s *p, double *x, const double *dinv);
+// one workgroup: rz, rr, beta, the counter, done and status
+int launch_cg_finish(const spmv_plan_s *p);
+// p = z + beta p, z formed again from r and dinv
+int launch_cg_direction(const spmv_plan_s *p, const double *dinv);
 int launch_hyb_overflow(const spmv_plan_s *p, const double *x, double *y);
 int launch_ss(const spmv_plan_s *p, const double *x, double *y);
 int launch_dia(const spmv_plan_s *p, const double *x, double *y, const Axpby *ab = nullptr,
@@ -740,5 +781,7 @@ SPMV_LOCAL int create_on_device(const DevCsr &A, spmv_options_t *opts, spmv_plan
 SPMV_LOCAL int create_staged_on_host(const DevCsr &A, const spmv_options_t &o, spmv_plan_t *out);
 // capi_execute.cpp: make the plan's device the current one
 SPMV_LOCAL int bind_device(const spmv_plan_s *p);
+// capi_execute.cpp: the solver's cached graph (the arena frees the rest of p->cg)
+SPMV_LOCAL void cg_graph_release(spmv_plan_s *p);
 
 }  // namespace spmv

@@ -56,32 +56,12 @@ __global__ __launch_bounds__(256) void dot_rows_kernel(const double *__restrict_
     dot_block_store(t, q, part);
 }
 
-// One workgroup of 16 waves.  Thread i takes slots i, i + 1024, ... ascending,
-// four 16-byte loads in flight and their adds in slot order; then the
-// butterfly, then the waves in wave order.  slots = 0 (m = 0): +0.0, +0.0.
-constexpr int kDotFinishThreads = 1024;
+// One workgroup of 16 waves adds the slots in the fixed order of
+// dot_slots_sum (device.hpp).  slots = 0 (m = 0): +0.0, +0.0.
 __global__ __launch_bounds__(kDotFinishThreads) void dot_finish_kernel(const double *__restrict__ part, int64_t slots,
                                                                       double *__restrict__ dots) {
-    constexpr int64_t T = kDotFinishThreads;
-    const f64x2 *ps = reinterpret_cast<const f64x2 *>(part);
-    double t = 0.0, q = 0.0;
-    int64_t i = threadIdx.x;
-    for (; i + 3 * T < slots; i += 4 * T) {
-        f64x2 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = ps[i + u * T];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            t = __dadd_rn(t, v[u].x);
-            q = __dadd_rn(q, v[u].y);
-        }
-    }
-    for (; i < slots; i += T) {
-        const f64x2 v = ps[i];
-        t = __dadd_rn(t, v.x);
-        q = __dadd_rn(q, v.y);
-    }
-    dot_block_sum<kDotFinishThreads / 64>(t, q);
+    double t, q;
+    dot_slots_sum(part, slots, t, q);
     if (threadIdx.x == 0) {
         dots[0] = t;
         dots[1] = q;
